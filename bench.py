@@ -7,8 +7,26 @@ slot-major SoA layout.  One step = one pass of the hot path over one batch
 of 2^20 groups.  ``--batches`` distinct batches (default 16, ~0.96 GB with
 outputs) stay resident in HBM and are visited round-robin, so every step
 streams its batch from HBM instead of the 256 MB Infinity Cache (the
-MALL-warm single-batch rate is reported beside it as ``value_mall_warm``,
-timed exactly as the headline).
+MALL-warm single-batch rate is reported beside it under ``--full`` as
+``value_mall_warm``, timed exactly as the headline).
+
+A plain run (``--gpus 1 --steps K --warmup W``) does only what the headline
+figure needs: set-up, clock-settle pre-roll, W warm-up steps, the K timed
+steps, then the JSON line (``ms_per_step`` = wall milliseconds per timed
+step).  Everything else the benchmark measures or checks runs under
+``--full``: the parity check against the C oracle, the CPU baseline, the
+MALL-warm pass, the other BASELINE configs and the SURVEY §8f rows of the
+default workload, and at N > 1 the timed node-wide collectives with their
+checks.  ``--no-parity`` / ``--no-cpu-baseline`` / ``--no-others`` switch
+single parts of a ``--full`` run off.
+
+``--dump-outputs DIR`` writes what the last timed step computed (the arrays
+a caller of the timed path receives) as ``DIR/<name>.npy`` right after the
+timed region: a u64 vector as two float64 files (``<name>_lo`` / ``_hi``,
+its low and high 32 bits, both exact), narrower integers as float32 /
+float64; at most 64 MB in all, larger outputs as a fixed seeded sample.  The
+inputs are seeded, so two builds run with the same arguments are comparable
+output for output.
 
 Launch pipeline: consecutive steps are independent batches, so they are
 issued round-robin on ``--streams`` HIP streams (default 2): the tail of one
@@ -22,15 +40,15 @@ layout); ``--workload tracker|tracker-csr`` runs configs[4] (the streaming
 MsgAppResp tracker step, 16M groups per GPU).  The default stays configs[1],
 the metric's headline config.
 
-Parity: after the timed region every workload checks its own output against
-the C oracle (oracle/quorum_oracle.c) bit for bit and reports ``"parity"``;
-a mismatch exits non-zero.
+Parity (``--full``): after the timed region every workload checks its own
+output against the C oracle (oracle/quorum_oracle.c) bit for bit and reports
+``"parity"``; a mismatch exits non-zero.
 
 Multi-GPU: one process per GPU.  ``--gpus N`` with no launcher spawns the N
 ranks itself (children get RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*; the
 parent touches no GPU); under torchrun ``--gpus`` must equal WORLD_SIZE.
 Groups shard by global group number (weak scaling, no collective in the
-timed region).  For N > 1 the node-wide collectives are timed after the
+timed region).  For N > 1 ``--full`` times the node-wide collectives after the
 region through the C ABI's RCCL communicator (etcd_amd/comm.py:
 qb_dev_allgather_results, qb_dev_route_records — what a Go embedder binds),
 and rank 0 checks the gathered vector against the oracle.
@@ -252,6 +270,53 @@ def load_traffic(workload_key: str):
         return d.get(workload_key, {}).get("hbm_bytes_per_launch")
     except (OSError, ValueError):
         return None
+
+
+# --------------------------------------------------------- output dumps ---
+
+DUMP_CAP_BYTES = 64 << 20
+DUMP_SEED = 0x5EED00D0
+
+
+def dump_outputs(dirname: str, arrays: dict, prefix: str = "", cap: int = DUMP_CAP_BYTES) -> dict:
+    """``--dump-outputs``: write the named integer tensors as
+    ``dirname/<prefix><name>.npy``.  int64 (the u64 indexes) becomes two
+    float64 files, ``<name>_lo`` and ``<name>_hi`` (low and high 32 bits:
+    float64 holds either half exactly, not a whole u64); int32 becomes
+    float64, 8- and 16-bit integers float32.  When everything together would
+    pass ``cap`` bytes, every tensor of more than 1 MiB is cut to the same
+    fraction of its (flattened) elements, drawn with replacement by a
+    generator seeded with DUMP_SEED — the same positions in every run — and
+    kept in ascending order.  Returns {file name: elements written}."""
+    os.makedirs(dirname, exist_ok=True)
+    width = {torch.int64: 16, torch.int32: 8}
+    size = {k: t.numel() * width.get(t.dtype, 4) for k, t in arrays.items()}
+    whole = sum(b for b in size.values() if b <= 1 << 20)  # small tensors are never cut
+    total = sum(size.values()) - whole
+    frac = min(1.0, (cap - whole) / total) if total else 1.0
+    gen = torch.Generator()
+    gen.manual_seed(DUMP_SEED)
+    written = {}
+
+    def save(name, a):
+        np.save(os.path.join(dirname, f"{prefix}{name}.npy"), a)
+        written[f"{prefix}{name}.npy"] = int(a.size)
+    for name, t in arrays.items():
+        t = t.reshape(-1)
+        if frac < 1.0 and size[name] > 1 << 20:
+            m = int(t.numel() * frac)
+            idx = torch.randint(0, t.numel(), (m,), generator=gen).sort().values
+            t = t[idx.to(t.device)]
+        a = t.cpu().numpy()
+        if a.dtype == np.int64:
+            u = a.view(np.uint64)
+            save(name + "_lo", (u & np.uint64(0xFFFFFFFF)).astype(np.float64))
+            save(name + "_hi", (u >> np.uint64(32)).astype(np.float64))
+        elif a.dtype == np.int32:
+            save(name, a.astype(np.float64))
+        else:
+            save(name, a.astype(np.float32))
+    return written
 
 
 # ---------------------------------------------------------- CPU baseline ---
@@ -771,8 +836,10 @@ def tracker_main(args, world, rank, dev, barrier):
     every collective)."""
     csr = args.workload == "tracker-csr"
     G = args.groups if args.groups != 1 << 20 else 1 << 24
-    K = args.steps if args.steps != 1000 else 20
+    K = args.steps if args.steps is not None else 20
     W = args.warmup if args.warmup is not None else 4
+    if K < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     nb = W + K
     skew = getattr(args, "skew", "none") or "none"
     terms = getattr(args, "terms", "wide") or "wide"
@@ -849,6 +916,12 @@ def tracker_main(args, world, rank, dev, barrier):
         for k in range(W, nb):
             step(batches[k])
     elapsed, step_s = yield from timed_region(region, [st], K, barrier)
+    if args.dump_outputs:
+        # what the caller of the step holds after the last timed tick: the
+        # leader state it advanced, and the stat counters of the timed ticks
+        dump_outputs(args.dump_outputs,
+                     {k: getattr(tr, k) for k in TRACKER_STATE + ("stats",)},
+                     prefix=f"rank{rank}_" if world > 1 else "", cap=DUMP_CAP_BYTES // world)
     stats = tr.stats_dict()
     parity = None
     if snaps is not None:
@@ -868,6 +941,7 @@ def tracker_main(args, world, rank, dev, barrier):
         t = torch.tensor([elapsed, step_s], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, step_s = (float(x) for x in t.tolist())
+    if world > 1 and args.full:
         route_ms, route_impl, delta_ms, delta_impl, delta_changed, collectives, note = \
             yield from _tracker_collectives(args, world, rank, dev, G, W, tr, batches, gen,
                                             restore, barrier)
@@ -1075,7 +1149,10 @@ def eval_main(args, world, rank, dev, barrier):
     csr = args.workload != "fixed"
     if args.warmup is None:
         args.warmup = 300 if csr else 2000
-    n, G, B, K, W = args.voters, args.groups, max(1, args.batches), args.steps, args.warmup
+    K = args.steps if args.steps is not None else 1000
+    if K < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
+    n, G, B, W = args.voters, args.groups, max(1, args.batches), args.warmup
     S = max(1, args.streams)
     if csr:
         # configs[2]: 16M ragged groups per GPU; configs[3]: 64M joint groups over
@@ -1221,14 +1298,23 @@ def eval_main(args, world, rank, dev, barrier):
     tstreams = [main_stream] if graph is not None else streams
     elapsed, avg_kernel_s = yield from timed_region(lambda: run_steps(K, fork=graph is not None),
                                                     tstreams, K, barrier)
+    if args.dump_outputs:
+        # the last timed step's batch: step k runs batch k % B (a graph of L
+        # steps restarts the rotation at every replay and at the remainder)
+        kl = K if graph is None or K < args.graph else (K % args.graph or args.graph)
+        c, v = outs[(kl - 1) % B]
+        dump_outputs(args.dump_outputs, {"commit": c, "vote": v},
+                     prefix=f"rank{rank}_" if world > 1 else "", cap=DUMP_CAP_BYTES // world)
 
-    # MALL-warm single-batch rate (informational): one batch (51 MB at
-    # configs[1], inside the 256 MB MALL) re-read K times, timed exactly as
-    # the region above (events on the launch streams, no fork/join)
-    run_steps(W, fixed_batch=0)
-    torch.cuda.synchronize()
-    warm_elapsed, warm_kernel_s = yield from timed_region(
-        lambda: run_steps(K, fixed_batch=0, fork=False), streams, K, barrier, "mall_warm")
+    warm_elapsed = warm_kernel_s = None
+    if args.full:
+        # MALL-warm single-batch rate (informational): one batch (51 MB at
+        # configs[1], inside the 256 MB MALL) re-read K times, timed exactly as
+        # the region above (events on the launch streams, no fork/join)
+        run_steps(W, fixed_batch=0)
+        torch.cuda.synchronize()
+        warm_elapsed, warm_kernel_s = yield from timed_region(
+            lambda: run_steps(K, fixed_batch=0, fork=False), streams, K, barrier, "mall_warm")
 
     # parity: every resident batch's outputs (the last values written by the
     # timed steps; the MALL-warm pass rewrote batch 0 with the same result)
@@ -1253,10 +1339,13 @@ def eval_main(args, world, rank, dev, barrier):
     yield "times"
     per_rank = _per_rank_values(rate_local, world)
     if world > 1:
-        t = torch.tensor([elapsed, warm_elapsed, avg_kernel_s, warm_kernel_s], dtype=torch.float64,
-                         device=dev)
+        t = torch.tensor([elapsed, warm_elapsed or 0.0, avg_kernel_s, warm_kernel_s or 0.0],
+                         dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, warm_elapsed, avg_kernel_s, warm_kernel_s = (float(x) for x in t.tolist())
+        elapsed, warm_t, avg_kernel_s, warm_k = (float(x) for x in t.tolist())
+        if args.full:
+            warm_elapsed, warm_kernel_s = warm_t, warm_k
+    if world > 1 and args.full:
         # node-wide result: all-gather one batch's commit (u64) and vote (u8)
         # vectors, timed after the region
         yield "comm"
@@ -1344,8 +1433,8 @@ def eval_main(args, world, rank, dev, barrier):
             "preroll_steps": preroll_steps,
             "settle_probes": settle_probes,
             "settle_last_ratio": settle_ratio,
-            "value_mall_warm": world * G * K / warm_elapsed,
-            "mall_warm_kernel_us": warm_kernel_s * 1e6,
+            "value_mall_warm": world * G * K / warm_elapsed if args.full else None,
+            "mall_warm_kernel_us": warm_kernel_s * 1e6 if args.full else None,
             "allgather_ms": allgather_ms,
             "allgather_impl": gather_impl,
             "collectives": collectives,
@@ -1359,7 +1448,7 @@ def eval_main(args, world, rank, dev, barrier):
 
 def next_rows():
     """SURVEY §8f rows and configs[0] (tools/bench_configs.py, GPU side only:
-    one device time per row) for the default run's line: the leader inbox
+    one device time per row) for the default --full run's line: the leader inbox
     step (4M groups), ReadIndex acks (4M leaders; local answers as
     ReadStates, the all-message form beside it), wire ingest (16M messages,
     group-row table), a conf change over 8M groups, the composed wire ->
@@ -1426,7 +1515,7 @@ TOP_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 
 def line_shape_errors(line: dict) -> list:
-    """What the default run's JSON line lacks (tests/test_bench_launcher.py
+    """What the default --full run's JSON line lacks (tests/test_bench_launcher.py
     checks committed lines with it): the contract keys, the roofline and CPU
     baseline at N = 1, and at every N the four other BASELINE configs with a
     per-rank value each — plus, at N > 1, each workload's timed collectives
@@ -1470,7 +1559,7 @@ def line_shape_errors(line: dict) -> list:
 
 
 def run_other(args, world, rank, dev, barrier):
-    """One secondary workload of the default run: the generator RankGuard.run
+    """One secondary workload of the default --full run: the generator RankGuard.run
     drives (its parity, its JSON dict)."""
     if getattr(args, "fake_workloads", False):
         return fake_main(args, world, rank, dev, barrier)
@@ -1501,6 +1590,7 @@ def fake_main(args, world, rank, dev, barrier):
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if world > 1 and args.full:
         yield "allgather_results"
         out = [torch.zeros(4, dtype=torch.int64) for _ in range(world)]
         t0 = time.perf_counter()
@@ -1528,7 +1618,18 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1,
                     help="ranks (one per GPU); without a launcher, > 1 spawns them")
-    ap.add_argument("--steps", type=int, default=1000)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (default 1000 for configs[1]-[3], 20 for the tracker "
+                         "workloads)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: parity against the C oracle, the CPU baseline, "
+                         "the MALL-warm pass, the other BASELINE configs and the SURVEY §8f rows "
+                         "(default workload), and at N > 1 the timed collectives and node-wide "
+                         "checks; a plain run sets up, warms up, times --steps steps and prints "
+                         "the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB: a fixed seeded sample of larger outputs)")
     ap.add_argument("--warmup", type=int, default=None,
                     help="untimed warm-up steps (default 2000 x ~9 us for configs[1], 300 x "
                          "~0.2 ms for the CSR workloads: ~20-60 ms of work lets the clocks "
@@ -1552,10 +1653,13 @@ def parse_args(argv=None):
     ap.add_argument("--streams", type=int, default=2, help="HIP streams the steps rotate over")
     ap.add_argument("--cpu-seconds", type=float, default=8.0,
                     help="CPU baseline budget (split over its legs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the post-region oracle check")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true",
+                    help="--full without the post-region oracle check")
     ap.add_argument("--no-others", action="store_true",
-                    help="the default (configs[1], N = 1) run skips the other BASELINE configs")
+                    help="--full on the default workload (configs[1]) without the other BASELINE "
+                         "configs and the §8f rows")
     ap.add_argument("--tracker-parity-groups", type=int, default=0,
                     help="tracker workloads: groups of the shard whose final state is checked "
                          "against the sequential oracle replay of every tick (0 = the whole shard "
@@ -1607,6 +1711,8 @@ def error_line(world: int, workload: str, err: str) -> dict:
 
 def main():
     args = parse_args()
+    if not args.full:  # a plain run: the headline's set-up, warm-up and timed steps only
+        args.no_parity = args.no_cpu_baseline = args.no_others = True
     world, rank, local, spawn = resolve_world(args.gpus, os.environ)
     if spawn:  # no GPU call has happened in this process
         sys.exit(spawn_ranks(world, sys.argv[1:], deadline_s=args.deadline_s))
@@ -1679,7 +1785,7 @@ def main():
             sub = argparse.Namespace(**vars(args))
             sub.workload, sub.steps, sub.warmup, sub.no_cpu_baseline = wl, 20, None, True
             sub.preroll_ms, sub.settle_ms = min(args.preroll_ms, 200.0), min(args.settle_ms, 1000.0)
-            sub.skew = "none"
+            sub.skew, sub.dump_outputs = "none", None
             try:
                 p2, o2 = guard.run(wl, lambda: run_other(sub, world, rank, dev, barrier))
             except WorkloadAborted as ex:  # every rank: reported in the line

@@ -95,12 +95,14 @@ def test_route_columns_normalised_or_refused():
 
 
 def test_default_run_secondary_configs_wiring():
-    """The default (configs[1], N = 1) run also measures configs[2]-[4] and
-    the §8f rows: the flags and the bench_configs entry points next_rows()
-    calls exist with the arguments it passes (the GPU side runs on the box)."""
+    """The default (configs[1], N = 1) run with --full also measures
+    configs[2]-[4] and the §8f rows: the flags and the bench_configs entry
+    points next_rows() calls exist with the arguments it passes (the GPU side
+    runs on the box)."""
     import inspect
     a = bench.parse_args([])
     assert a.workload == "fixed" and not a.no_others
+    assert not a.full and bench.parse_args(["--full"]).full
     assert bench.parse_args(["--no-others"]).no_others
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import bench_configs as bc
@@ -187,11 +189,88 @@ def _fake_run(*extra, timeout=240):
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     t0 = __import__("time").monotonic()
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full",
                           "--fake-workloads", *extra], env=env, capture_output=True, text=True,
                          timeout=timeout)
     lines = [json.loads(x) for x in out.stdout.splitlines() if x.startswith("{")]
     return out, lines, __import__("time").monotonic() - t0
+
+
+def test_plain_fake_world2_run_is_the_headline_alone():
+    """Without --full the same launcher and main loop run the headline
+    workload only: no other configs, no timed collectives, no node-wide
+    check — and the line still carries the contract keys."""
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2",
+                          "--fake-workloads"], env=env, capture_output=True, text=True, timeout=240)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [json.loads(x) for x in out.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1
+    line = lines[0]
+    assert "other_configs" not in line and "next_rows" not in line and "cpu_baseline" not in line
+    assert line["collectives"] == {} and "node-wide" not in line["parity"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert line[k] is not None, k
+    assert line["n_gpus"] == 2 and len(line["value_per_rank"]) == 2
+
+
+def test_steps_default_is_per_workload_and_explicit_steps_are_kept():
+    """--steps has no sentinel value: unset it is None (each workload picks
+    its default), and 1000 on the command line means 1000."""
+    assert bench.parse_args([]).steps is None
+    assert bench.parse_args(["--steps", "1000"]).steps == 1000
+    assert bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+    assert bench.parse_args([]).dump_outputs is None
+
+
+def test_dump_outputs_exact_halves_and_types(tmp_path):
+    """A u64 vector is written as two float64 files that rebuild it bit for
+    bit (values past 2^53 included); int32 as float64, bytes as float32."""
+    import numpy as np
+    u = np.array([0, 1, (1 << 53) + 1, (1 << 63) | 0x3FFFFF0000000007, (1 << 64) - 1], np.uint64)
+    arrays = {"commit": torch.from_numpy(u.view(np.int64).copy()),
+              "vote": torch.tensor([1, 2, 3, 0, 255], dtype=torch.uint8),
+              "stepdown_at": torch.tensor([-1, 7, 1 << 30, 0, 5], dtype=torch.int32),
+              "active": torch.tensor([-1, 0, 3, 1 << 14, 9], dtype=torch.int16)}
+    written = bench.dump_outputs(str(tmp_path), arrays)
+    assert sorted(written) == ["active.npy", "commit_hi.npy", "commit_lo.npy", "stepdown_at.npy",
+                               "vote.npy"]
+    lo, hi = np.load(tmp_path / "commit_lo.npy"), np.load(tmp_path / "commit_hi.npy")
+    assert lo.dtype == hi.dtype == np.float64
+    assert np.array_equal((hi.astype(np.uint64) << np.uint64(32)) | lo.astype(np.uint64), u)
+    v = np.load(tmp_path / "vote.npy")
+    assert v.dtype == np.float32 and v.tolist() == [1, 2, 3, 0, 255]
+    s = np.load(tmp_path / "stepdown_at.npy")
+    assert s.dtype == np.float64 and s.tolist() == [-1, 7, 1 << 30, 0, 5]
+    a = np.load(tmp_path / "active.npy")
+    assert a.dtype == np.float32 and a.tolist() == [-1, 0, 3, 1 << 14, 9]
+
+
+def test_dump_outputs_sample_is_capped_and_the_same_every_run(tmp_path):
+    """Outputs past the cap: every large tensor is cut to the same fraction
+    at seeded positions (two dumps agree file for file, and the sample is
+    drawn from the tensor in ascending position order), small tensors stay
+    whole, and the files together stay under the cap."""
+    import numpy as np
+    n = 1 << 19
+    arrays = {"commit": torch.arange(n, dtype=torch.int64) * 3,        # 8 MiB as lo + hi
+              "vote": (torch.arange(n) % 251).to(torch.uint8),          # 2 MiB as float32
+              "stats": torch.arange(8, dtype=torch.int64)}
+    cap = 2 << 20
+    a, b = tmp_path / "a", tmp_path / "b"
+    wa = bench.dump_outputs(str(a), arrays, cap=cap)
+    wb = bench.dump_outputs(str(b), arrays, cap=cap)
+    assert wa == wb and wa["stats_lo.npy"] == 8
+    size = 0
+    for name in wa:
+        x, y = np.load(a / name), np.load(b / name)
+        assert np.array_equal(x, y), name
+        size += x.nbytes
+    assert cap // 2 < size <= cap
+    lo = np.load(a / "commit_lo.npy")
+    assert 0 < lo.size < n and np.all(np.diff(lo) >= 0) and np.all(lo % 3 == 0)
+    assert wa["vote.npy"] == wa["commit_lo.npy"] == wa["commit_hi.npy"]  # one fraction for all
 
 
 def test_fake_world2_run_reports_every_workload():

@@ -7,11 +7,11 @@
 set -o pipefail
 O=${1:?outdir}; mkdir -p $O/pmc; export TMPDIR=/tmp
 bash tools/gpu/run.sh $O info tests smoke || exit 1
-timeout -k 10 400 python3 -u bench.py --gpus 1 --steps 20 --warmup 5 \
+timeout -k 10 400 python3 -u bench.py --gpus 1 --steps 20 --warmup 5 --full \
   > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err || { echo "bench failed"; tail -20 $O/bench_driver_cmd.err; exit 1; }
 echo "driver command ok"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/driver_trace -o run -- \
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline \
+  python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline \
   > $O/driver_cmd_under_rocprof.json 2> $O/driver_trace.err || { echo "trace failed"; exit 1; }
 echo "driver trace ok"
 for c in FETCH_SIZE WRITE_SIZE; do

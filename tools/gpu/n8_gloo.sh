@@ -6,7 +6,7 @@ set -o pipefail
 O=${1:?outdir}
 mkdir -p $O
 s=$(date +%s)
-timeout -k 10 1000 python -u bench.py --gpus 8 --backend gloo --steps 20 --warmup 5 \
+timeout -k 10 1000 python -u bench.py --gpus 8 --backend gloo --steps 20 --warmup 5 --full \
   > $O/bench_n8_gloo.json 2> $O/bench_n8_gloo.err
 rc=$?
 echo "rc=$rc wall_s=$(( $(date +%s) - s ))" | tee $O/bench_n8_gloo.wall

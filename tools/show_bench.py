@@ -15,5 +15,5 @@ for path in sys.argv[1:]:
         cb = d.get("cpu_baseline") or {}
         print(f"{path}: value {d['value']:.4g} {d['unit']}  ms/step {d['ms_per_step']:.4f}  "
               f"kern {r['avg_kernel_us']:.2f}us  {r['achieved']:.0f} GB/s frac {r['frac']:.3f}  "
-              f"warm {d.get('value_mall_warm', 0):.4g}  cpu {cb.get('value', 0):.4g}  "
+              f"warm {d.get('value_mall_warm') or 0:.4g}  cpu {cb.get('value', 0):.4g}  "
               f"ag {d.get('allgather_ms')}")
