@@ -18,6 +18,7 @@ import torch
 
 from . import batch
 from .batch import INDEX_INF
+from .tick import TickResult, TickState, leader_tick
 
 MAX_UINT64 = INDEX_INF
 
@@ -173,5 +174,5 @@ def vote_results(configs: Sequence[JointConfig], votes: Sequence[Mapping[int, bo
 
 
 __all__ = ["AckedIndexer", "INDEX_INF", "JointConfig", "MAX_UINT64", "MajorityConfig",
-           "MapAckIndexer", "VoteLost", "VotePending", "VoteResult", "VoteWon", "batch",
-           "committed_indexes", "index_string", "vote_results"]
+           "MapAckIndexer", "TickResult", "TickState", "VoteLost", "VotePending", "VoteResult",
+           "VoteWon", "batch", "committed_indexes", "index_string", "leader_tick", "vote_results"]

@@ -348,6 +348,13 @@ class LeaderGroups:
             stats={k: st[i] for i, k in enumerate(LSTAT_NAMES)},
             read_states=rs, read_off=roff)
 
+    def tick(self, state, election_timeout: int, heartbeat_timeout: int, check_quorum: bool,
+             stream=None, out=None):
+        """One raft.tick() over these groups (etcd_amd.quorum.tick.leader_tick)."""
+        from .tick import leader_tick
+        return leader_tick(self, state, election_timeout, heartbeat_timeout, check_quorum,
+                           stream, out=out)
+
     def _outbox(self, nchunks: int, read_states: bool = False):
         dev, G = self.device, self.G
         key = ("outbox", nchunks, read_states)

@@ -627,6 +627,113 @@ int qb_dev_leader_step_outbox(const qb_leader_groups* lg, const qb_leader_inbox*
                               size_t workspace_bytes, void* stream);
 
 /* ----------------------------------------------------------------------- */
+/* Leader tick: heartbeats, CheckQuorum sweep, election timers             */
+/* ----------------------------------------------------------------------- */
+
+/* raft.tick() (tickElection / tickHeartbeat, raft.go:645-684) for G groups in
+ * one call: what a multi-raft host runs once per tick interval for every
+ * group it hosts.  Per group, groups independent:
+ *   not a leader (tickElection): electionElapsed++; a promotable node past
+ *     its randomized timeout (raft.go:1618-1621, 1714-1716) resets the
+ *     counter and gets QB_TFLAG_HUP — the campaign (Step MsgHup) is the
+ *     host's;
+ *   leader (tickHeartbeat): both counters++.  At electionElapsed >=
+ *     election_timeout the counter resets and, with check_quorum, the
+ *     MsgCheckQuorum step runs (raft.go:997-1018): the leader's own Progress
+ *     is marked RecentActive (if it has one), ProgressTracker.QuorumActive
+ *     (tracker/tracker.go:215-225: RecentActive of every voter, learners
+ *     skipped, VoteWon in both halves, an empty half wins — the rule of
+ *     qb_dev_csr_quorum_active) decides whether the leader steps down, and
+ *     QB_PR_RECENT_ACTIVE is cleared on every slot but the leader's
+ *     (learners included).  A leader that stays one drops a pending
+ *     leadership transfer (meta transferee := 0xFF, raft.go:669-671,
+ *     QB_TFLAG_TRANSFER_ABORTED).  A leader that stays one and whose
+ *     heartbeatElapsed >= heartbeat_timeout resets that counter and
+ *     broadcasts (MsgBeat -> bcastHeartbeat, raft.go:994-996, 495-541): for
+ *     every slot s but its own, voters and learners, hb_commit[s] =
+ *     min(match[s], committed[g]), and hb_ctx[g] = the context of the newest
+ *     pending ReadIndex request (read_only.go:116-121: rq_ctx[g * readq_cap +
+ *     nq - 1], 0 if the queue is empty).
+ * Step-down is becomeFollower(r.Term, None) -> reset (raft.go:590-619)
+ * restricted to the fields this call owns: role := Follower (every other
+ * bit of the role byte kept), both counters 0, meta transferee := 0xFF
+ * (without QB_TFLAG_TRANSFER_ABORTED), QB_PR_RECENT_ACTIVE cleared on every
+ * slot (reset zeroes the leader's own Progress too), QB_TFLAG_STEPPED_DOWN;
+ * a leader that steps down sends no heartbeat on that tick.  The rest of
+ * reset stays the host's, as stepdown_at is for the leader step: Match / Next
+ * / Inflights, readOnly, the votes, lead and the new randomized timeout.
+ *
+ * The host forms the heartbeats of a group with QB_TFLAG_BEAT as
+ *   pb.Message{Type: MsgHeartbeat (QB_MSG_HEARTBEAT), To: ids[s], From: its own
+ *              ID, Term: term[g], Commit: hb_commit[s], Context: hb_ctx[g]}
+ * for every slot s of the group but the leader's, ascending — the order of
+ * ProgressTracker.Visit (tracker.go:191-212; ascending IDs are ascending CSR
+ * slots); hb_ctx 0 is the empty context, anything else the request's 8-byte
+ * big-endian id.  Heartbeats stay slot-aligned: 8 bytes per peer.
+ *
+ * A leader slot (meta bits 0-7) >= the group's slot count means the leader
+ * has no Progress (raft.go:998-1006): nothing is self-activated and every
+ * slot gets a heartbeat.  A slot count above QB_MAX_SLOTS is read as
+ * QB_MAX_SLOTS and a request count above readq_cap as readq_cap; the tick
+ * never reads or writes outside the caller's arrays. */
+#define QB_MSG_HEARTBEAT 8 /* pb.MsgHeartbeat (raft.pb.go:76-94) */
+
+/* role byte: raft.StateType (raft.go:39-45) in bits 0-1 | flags. */
+#define QB_ROLE_FOLLOWER 0
+#define QB_ROLE_CANDIDATE 1
+#define QB_ROLE_LEADER 2
+#define QB_ROLE_PRE_CANDIDATE 3
+#define QB_ROLE_PROMOTABLE 0x80u /* raft.promotable(), maintained by the host */
+
+/* Per-group output flags of the tick. */
+#define QB_TFLAG_HUP 0x01u              /* election timeout: the host campaigns */
+#define QB_TFLAG_BEAT 0x02u             /* heartbeats written                   */
+#define QB_TFLAG_STEPPED_DOWN 0x04u     /* CheckQuorum failed (= QB_LFLAG_STEPPED_DOWN) */
+#define QB_TFLAG_CHECK_QUORUM 0x08u     /* the MsgCheckQuorum step ran          */
+#define QB_TFLAG_TRANSFER_ABORTED 0x10u /* the lead transfer timed out          */
+
+enum {
+  QB_TSTAT_LEADERS = 0,          /* groups ticked as leader (tickHeartbeat)    */
+  QB_TSTAT_NON_LEADERS = 1,      /* groups ticked otherwise (tickElection)     */
+  QB_TSTAT_BEATS = 2,            /* groups that broadcast                      */
+  QB_TSTAT_HEARTBEATS = 3,       /* heartbeats sent (hb_commit entries written) */
+  QB_TSTAT_CHECK_QUORUM = 4,     /* MsgCheckQuorum steps                       */
+  QB_TSTAT_STEPPED_DOWN = 5,     /* leaders that stepped down                  */
+  QB_TSTAT_TRANSFER_ABORTED = 6, /* lead transfers aborted                     */
+  QB_TSTAT_HUPS = 7,             /* election timeouts                          */
+  QB_TSTAT_COUNT = 8
+};
+
+/* The arrays are those of qb_leader_groups (same layouts: a caller passes the
+ * same buffers) plus the tick's own per-group state. */
+typedef struct qb_tick_groups {
+  uint64_t G;
+  uint32_t readq_cap;         /* 0..QB_LEADER_MAX_READQ                       */
+  uint32_t election_timeout;  /* raft.electionTimeout (ticks, >= 1)           */
+  uint32_t heartbeat_timeout; /* raft.heartbeatTimeout (ticks, >= 1)          */
+  uint32_t check_quorum;      /* raft.checkQuorum: 0 / 1                      */
+  const uint32_t* off;        /* [G+1] */
+  const uint32_t* cfg;        /* [G] */
+  uint32_t* meta;             /* [G] in/out: only bits 8-15 (transferee) may change */
+  const uint64_t* committed;  /* [G] */
+  const uint64_t* match;      /* [off[G]] */
+  uint8_t* pstate;            /* [off[G]] in/out: only QB_PR_RECENT_ACTIVE may change */
+  const uint64_t* rq_ctx;     /* [G * readq_cap]; NULL iff readq_cap == 0     */
+  uint8_t* role;              /* [G] in/out: QB_ROLE_*                        */
+  uint32_t* election_elapsed; /* [G] in/out */
+  uint32_t* heartbeat_elapsed; /* [G] in/out */
+  const uint32_t* rand_timeout; /* [G] raft.randomizedElectionTimeout         */
+} qb_tick_groups;
+
+/* tflags [G]: QB_TFLAG_*, written for every group (0 where nothing fired).
+ * hb_commit [off[G]] / hb_ctx [G]: written only where a heartbeat is sent
+ * (a beating group's peer slots / a beating group); every other element is
+ * left untouched.  stats: QB_TSTAT_COUNT device uint64 (accumulated).
+ * G == 0 is QB_OK and writes nothing; everything else is required. */
+int qb_dev_leader_tick(const qb_tick_groups* tg, uint8_t* tflags, uint64_t* hb_commit,
+                       uint64_t* hb_ctx, uint64_t* stats, void* stream);
+
+/* ----------------------------------------------------------------------- */
 /* Wire ingest                                       */
 /* ----------------------------------------------------------------------- */
 

@@ -856,6 +856,141 @@ def readindex_config(G, reps, Q=4, *, reporter=None, gpu_only=None):
             **cq})
 
 
+def tick_config(G, reps, *, reporter=None):
+    """The batched raft tick (qb_dev_leader_tick): G five-voter leader groups
+    of the synth_streaming state with etcd's defaults (ElectionTick 10,
+    HeartbeatTick 1, CheckQuorum): every tick broadcasts, every tenth also
+    sweeps.  A sample is ten consecutive ticks from zeroed counters — nine beat
+    ticks and one that sweeps and beats — with one event per tick; the
+    RecentActive bits the sweep clears and the counters are restored between
+    samples, outside the timed ticks (the responses that set them again are
+    the leader step's).  Parity: the same table at the same size with seeded
+    RecentActive bits, counters, transfers and a share of non-leaders, ten
+    ticks against the numpy restatement (tests/tick_pack.py np_tick, itself
+    checked against tests/tick_ref.py in tests/test_tick_ref.py)."""
+    reporter = reporter or report
+    from etcd_amd.quorum import tick as qt
+    from etcd_amd.quorum.leader import _to_np, synth_streaming
+    from tests import tick_pack as P
+    ET, HT, CQ, n, TICKS = 10, 1, 1, 5, 10
+    lg, _ = synth_streaming(G, W=1, D=1, n=n, device=dev)
+    S = lg.S
+    z32 = lambda: torch.zeros(G, dtype=torch.int32, device=dev)  # noqa: E731
+    state = qt.TickState(torch.full((G,), qt.ROLE_LEADER | qt.ROLE_PROMOTABLE, dtype=torch.uint8,
+                                    device=dev), z32(), z32(),
+                         torch.full((G,), 15, dtype=torch.int32, device=dev))
+    pstate0 = lg.t["pstate"].clone()
+    out = lg.tick(state, ET, HT, True)   # (the mirror's argument checks, once)
+    sp = torch.cuda.current_stream(dev).cuda_stream
+    # the timed calls go to the C ABI with the struct built once: the mirror's
+    # per-call checks cost about as much host time as the kernel runs
+    import ctypes as C
+    from etcd_amd import _lib
+    tg = qt.TickGroupsC(G=G, readq_cap=0, election_timeout=ET, heartbeat_timeout=HT,
+                        check_quorum=CQ, rq_ctx=None,
+                        **{k: lg.t[k].data_ptr() for k in ("off", "cfg", "meta", "committed", "match",
+                                                           "pstate")},
+                        role=state.role.data_ptr(),
+                        election_elapsed=state.election_elapsed.data_ptr(),
+                        heartbeat_elapsed=state.heartbeat_elapsed.data_ptr(),
+                        rand_timeout=state.rand_timeout.data_ptr())
+    fn = _lib.fn("qb_dev_leader_tick")
+    args = (C.byref(tg), out.tflags.data_ptr(), out.hb_commit.data_ptr(), out.hb_ctx.data_ptr(),
+            out.stats.data_ptr(), sp)
+
+    def tick():
+        _lib.check(fn(*args), "qb_dev_leader_tick")
+
+    def restore():
+        lg.t["pstate"].copy_(pstate0)
+        state.election_elapsed.zero_()
+        state.heartbeat_elapsed.zero_()
+
+    def sample(ev):
+        restore()
+        torch.cuda.synchronize()
+        for k in range(TICKS):
+            ev.record(ev.ev[k], sp)
+            tick()
+        ev.record(ev.ev[TICKS], sp)
+        torch.cuda.synchronize()
+        return [ev.elapsed_ms(k, k + 1) / 1e3 for k in range(TICKS)]
+    import time
+    ev = HipEvents(TICKS + 1)
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < 0.3:  # warm-up: clocks settle (time_region)
+        sample(ev)
+    out.stats.zero_()
+    per = np.array([sample(ev) for _ in range(reps)])
+    ev.close()
+    st = out.stats_dict()
+    assert st["beats"] == reps * TICKS * G and st["check_quorum"] == reps * G, st
+    assert st["stepped_down"] == 0 and st["heartbeats"] == reps * TICKS * G * (n - 1), st
+    t_tick = float(np.median(per.sum(axis=1))) / TICKS
+    t_beat = float(np.median(per[:, :TICKS - 1]))
+    t_sweep = float(np.median(per[:, TICKS - 1]))
+    # per group and beat tick: off 4, role 1, both counters read and written
+    # 16, meta 4, committed 8, tflags 1, hb_ctx 8 = 42 B, and per peer slot
+    # match 8 in + hb_commit 8 out (the leader's own slot is not read);
+    # the sweep tick adds cfg 4, the pstate bytes read (n) and the n - 1
+    # cleared ones written
+    beat_b = 42 + (n - 1) * 16
+    sweep_b = beat_b + 4 + n + (n - 1)
+    algo = G * (beat_b * (TICKS - 1) + sweep_b) / TICKS
+    extra = {"unit": "group-ticks/s", "ticks_per_sample": TICKS, "samples": reps,
+             "beat_tick_us": t_beat * 1e6, "beat_tick_bytes_per_group": beat_b,
+             "beat_tick_frac": G * beat_b / t_beat / 1e9 / HBM_PEAK_GBS,
+             "sweep_tick_us": t_sweep * 1e6, "sweep_tick_bytes_per_group": sweep_b,
+             "sweep_tick_frac": G * sweep_b / t_sweep / 1e9 / HBM_PEAK_GBS,
+             "election_tick": ET, "heartbeat_tick": HT, "check_quorum": CQ,
+             "timing": "one HIP event per tick, median over samples of 10 consecutive ticks; "
+                       "per_launch_us = median sample / 10"}
+    # parity at this size
+    gen = torch.Generator(device=dev).manual_seed(0x71C4)
+    rnd = lambda hi, k: torch.randint(0, hi, (k,), generator=gen, device=dev)  # noqa: E731
+    lg.t["pstate"].copy_((1 | (rnd(2, S) << 3)).to(torch.uint8))
+    lg.t["meta"].copy_((lg.t["meta"] & ~0xFF00
+                        | torch.where(rnd(8, G) == 0, rnd(n, G), torch.full((G,), 0xFF, device=dev))
+                        << 8).to(torch.int32))
+    role = torch.where(rnd(16, G) == 0, rnd(4, G), torch.full((G,), 2, device=dev)) | (rnd(2, G) << 7)
+    state.role.copy_(role.to(torch.uint8))
+    state.election_elapsed.copy_(rnd(ET + 6, G).to(torch.int32))
+    state.heartbeat_elapsed.copy_(rnd(3, G).to(torch.int32))
+    state.rand_timeout.copy_((ET + rnd(ET, G)).to(torch.int32))
+    a = {k: _to_np(lg.t[k], dt).copy() for k, dt in (
+        ("off", np.uint32), ("cfg", np.uint32), ("meta", np.uint32), ("committed", np.uint64),
+        ("match", np.uint64), ("pstate", np.uint8))}
+    t = {k: v.copy() for k, v in state.numpy(G).items()}
+    fill = P.FILL - (1 << 64)
+    out.hb_commit.fill_(fill)
+    out.hb_ctx.fill_(fill)
+    out.stats.zero_()
+    hc, hx = np.full(S, P.FILL, np.uint64), np.full(G, P.FILL, np.uint64)
+    want_st = {k: 0 for k in qt.TSTAT_NAMES}
+    ok = True
+    for k in range(TICKS):
+        tick()
+        tf, st1 = P.np_tick(a, t, 0, ET, HT, CQ, hc, hx)
+        for key, v in st1.items():
+            want_st[key] += v
+        ok = ok and np.array_equal(out.tflags.cpu().numpy()[:G], tf)
+    got_t = state.numpy(G)
+    ok = (ok and all(np.array_equal(got_t[key], t[key]) for key in t)
+          and np.array_equal(_to_np(lg.t["meta"], np.uint32, G), a["meta"])
+          and np.array_equal(_to_np(lg.t["pstate"], np.uint8, S), a["pstate"])
+          and np.array_equal(_to_np(out.hb_commit, np.uint64, S), hc)
+          and np.array_equal(_to_np(out.hb_ctx, np.uint64, G), hx)
+          and out.stats_dict() == want_st)
+    extra["parity"] = bool(ok)
+    extra["parity_check"] = (f"{G} groups, seeded RecentActive bits / counters / transfers / roles, "
+                             f"{TICKS} ticks vs the numpy restatement of tests/tick_ref.py: tflags "
+                             "every tick; counters, role, meta, pstate, hb_commit and hb_ctx "
+                             "(untouched elements included) and the stats after the last: "
+                             f"{want_st}")
+    reporter("raft tick (heartbeats, CheckQuorum sweep, election timers)", G, t_tick, algo, extra)
+    assert ok, "tick parity failed"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -893,6 +1028,8 @@ def main():
         readindex_config(1 << 22, a.reps)
     if "confchange" in which:
         confchange_config(1 << 23, a.reps)
+    if "tick" in which:
+        tick_config(1 << 22, a.reps)
     if "wire-tracker" in which:
         wire_tracker_config(1 << 24, a.reps)
     if "wire-tracker-fused" in which:  # development A/B: the one call alone
