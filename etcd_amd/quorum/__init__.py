@@ -18,6 +18,7 @@ import torch
 
 from . import batch
 from .batch import INDEX_INF
+from .follower import FollowerGroups, FollowerInbox, FollowerResult, follower_step
 from .tick import TickResult, TickState, leader_tick
 
 MAX_UINT64 = INDEX_INF
@@ -173,6 +174,7 @@ def vote_results(configs: Sequence[JointConfig], votes: Sequence[Mapping[int, bo
     return [VoteResult(int(x)) for x in out]
 
 
-__all__ = ["AckedIndexer", "INDEX_INF", "JointConfig", "MAX_UINT64", "MajorityConfig",
-           "MapAckIndexer", "TickResult", "TickState", "VoteLost", "VotePending", "VoteResult",
-           "VoteWon", "batch", "committed_indexes", "index_string", "leader_tick", "vote_results"]
+__all__ = ["AckedIndexer", "FollowerGroups", "FollowerInbox", "FollowerResult", "INDEX_INF",
+           "JointConfig", "MAX_UINT64", "MajorityConfig", "MapAckIndexer", "TickResult",
+           "TickState", "VoteLost", "VotePending", "VoteResult", "VoteWon", "batch", "committed_indexes", "follower_step", "index_string", "leader_tick",
+           "vote_results"]

@@ -734,6 +734,145 @@ int qb_dev_leader_tick(const qb_tick_groups* tg, uint8_t* tflags, uint64_t* hb_c
                        uint64_t* hb_ctx, uint64_t* stats, void* stream);
 
 /* ----------------------------------------------------------------------- */
+/* Follower step: heartbeats, vote requests, MsgTimeoutNow                 */
+/* ----------------------------------------------------------------------- */
+
+/* raft.Step (raft.go:847-984) for the inbox of nodes that receive
+ * MsgHeartbeat / MsgVote / MsgPreVote / MsgTimeoutNow, for G groups in one
+ * call: the receiving side of qb_dev_leader_tick's heartbeats, of
+ * QB_MSG_TIMEOUT_NOW and of the requests whose answers qb_dev_record_votes
+ * consumes.  Each group's records are applied in batch order; groups are
+ * independent.  No configuration and no Progress are read: Step checks no
+ * membership for these types and learners vote too (raft.go:939-956).
+ *
+ * Term filter (raft.go:849-920), per record with Term != 0 (0 is a local
+ * message and skips it):
+ *   higher term: a MsgVote / MsgPreVote with check_quorum && lead != 0 &&
+ *     election_elapsed < election_timeout and without QB_FREC_FORCE is
+ *     dropped (the leader's lease).  MsgPreVote never changes the term; a
+ *     heartbeat runs becomeFollower(m.Term, m.From), a MsgVote or
+ *     MsgTimeoutNow becomeFollower(m.Term, None);
+ *   lower term: a heartbeat with check_quorum || pre_vote is answered with
+ *     MsgAppResp (raft.go:906; send stamps Term = term[g]), a MsgPreVote
+ *     with MsgPreVoteResp, Reject, Term = term[g]; anything else is ignored.
+ * becomeFollower -> reset (raft.go:686-693, 590-619), restricted to the
+ * fields this call owns: term (and vote := 0) change only if the term
+ * differs, lead is set, both counters 0, role := Follower with the other bits
+ * of the byte kept, QB_FFLAG_RESET.  The rest of reset stays the host's, as
+ * for the tick: Progress, the votes, readOnly, the transferee and the new
+ * randomized timeout.
+ * MsgVote / MsgPreVote (raft.go:930-978), in any role: canVote = vote == From
+ *   || (vote == 0 && lead == 0) || (MsgPreVote && m.Term > term), and
+ *   raftLog.isUpToDate(Index, LogTerm) (log.go:316-318) against last_term /
+ *   last_index.  A grant answers with Term = m.Term, and for MsgVote only sets
+ *   election_elapsed = 0 and vote = From; a rejection answers with Term =
+ *   term[g] and Reject.
+ * MsgHeartbeat at or above the term: a follower sets election_elapsed = 0 and
+ *   lead = From (raft.go:1437-1440), a (pre-)candidate first runs
+ *   becomeFollower(m.Term, m.From) (raft.go:1393-1395); then handleHeartbeat
+ *   (raft.go:1513-1516): committed = max(committed, Commit) and a
+ *   MsgHeartbeatResp with Term = term[g] (the host copies the record's
+ *   context).  A leader ignores it (stepLeader has no case for it).
+ * MsgTimeoutNow (raft.go:1415-1416, 1452-1457, 760-768): only a follower with
+ *   QB_ROLE_PROMOTABLE acts on it; the campaign is the host's, so the group
+ *   stops there (below).  Every other role ignores it.
+ *
+ * Stops.  stop_at[g] = batch index of the first record whose effect is the
+ * host's, UINT32_MAX if none:
+ *   a QB_FIN_HOST record (a message the host steps itself: MsgApp, MsgSnap,
+ *     MsgProp, ...; it is in the batch only to keep the order): nothing of it
+ *     is applied, QB_FFLAG_HOST_MSG;
+ *   the MsgTimeoutNow of a promotable follower: the term filter's effect is
+ *     kept, QB_FFLAG_CAMPAIGN;
+ *   a heartbeat that would reach commitTo with committed < Commit &&
+ *     last_index < Commit (Go panics, log.go:236-244): nothing of it is
+ *     applied, QB_FFLAG_COMMIT_RANGE.
+ * The group's records behind the stop are not applied, get no response and
+ * count as QB_FSTAT_AFTER_STOP; the host re-submits them.
+ *
+ * Responses are record-aligned (a record yields at most one message):
+ * resp_type[i] = pb MessageType | QB_FRESP_REJECT, 0 = no message;
+ * resp_term[i] = Message.Term; To = from[i].  Both are written for every
+ * record.  gflags[g] (QB_FFLAG_*) and stop_at[g] are written for every group.
+ * QB_FFLAG_HARDSTATE: term, vote or committed differ from their values at
+ * entry — what Ready persists before the responses may be sent. */
+#define QB_FIN_HEARTBEAT 0
+#define QB_FIN_VOTE 1
+#define QB_FIN_PREVOTE 2
+#define QB_FIN_TIMEOUT_NOW 3
+#define QB_FIN_HOST 4
+#define QB_FREC_KIND_MASK 0x07u
+#define QB_FREC_FORCE 0x80u /* Context == "CampaignTransfer" (raft.go:854) */
+
+#define QB_FRESP_APP_RESP 4        /* pb.MsgAppResp       */
+#define QB_FRESP_VOTE_RESP 6       /* pb.MsgVoteResp      */
+#define QB_FRESP_HEARTBEAT_RESP 9  /* pb.MsgHeartbeatResp */
+#define QB_FRESP_PREVOTE_RESP 18   /* pb.MsgPreVoteResp   */
+#define QB_FRESP_REJECT 0x80u
+
+#define QB_FFLAG_HOST_MSG 0x01u     /* stopped at a QB_FIN_HOST record        */
+#define QB_FFLAG_CAMPAIGN 0x02u     /* stopped at MsgTimeoutNow: hup(transfer) */
+#define QB_FFLAG_COMMIT_RANGE 0x04u /* stopped at a Commit past last_index    */
+#define QB_FFLAG_RESET 0x08u        /* becomeFollower ran: the host's reset   */
+#define QB_FFLAG_HARDSTATE 0x10u    /* term / vote / committed changed        */
+
+enum {
+  QB_FSTAT_HEARTBEATS = 0,      /* heartbeats handled (handleHeartbeat)       */
+  QB_FSTAT_GRANTED = 1,         /* (pre-)votes granted                        */
+  QB_FSTAT_REJECTED = 2,        /* (pre-)votes rejected at or above the term  */
+  QB_FSTAT_LEASE_DROPPED = 3,   /* higher-term (pre-)votes dropped in lease   */
+  QB_FSTAT_STALE_IGNORED = 4,   /* lower-term records ignored                 */
+  QB_FSTAT_STALE_ANSWERED = 5,  /* lower-term records answered                */
+  QB_FSTAT_ROLE_IGNORED = 6,    /* records the node's role ignores            */
+  QB_FSTAT_BECAME_FOLLOWER = 7, /* becomeFollower calls                       */
+  QB_FSTAT_AFTER_STOP = 8,      /* records behind their group's stop          */
+  QB_FSTAT_BAD_GROUP = 9,       /* group >= G, dropped                        */
+  QB_FSTAT_BAD_KIND = 10,       /* kind above QB_FIN_HOST, dropped            */
+  QB_FSTAT_COUNT = 11
+};
+
+/* role / election_elapsed / heartbeat_elapsed are the tick's buffers (same
+ * layouts: a caller passes the same arrays to both calls). */
+typedef struct qb_follower_groups {
+  uint64_t G;
+  uint32_t election_timeout;   /* raft.electionTimeout (ticks, >= 1)          */
+  uint32_t check_quorum;       /* raft.checkQuorum: 0 / 1                     */
+  uint32_t pre_vote;           /* raft.preVote: 0 / 1                         */
+  uint32_t reserved;           /* 0                                           */
+  uint64_t* term;              /* [G] in/out                                  */
+  uint64_t* vote;              /* [G] in/out: raft ID, 0 = None               */
+  uint64_t* lead;              /* [G] in/out: raft ID, 0 = None               */
+  uint64_t* committed;         /* [G] in/out                                  */
+  const uint64_t* last_index;  /* [G] raftLog.lastIndex()                     */
+  const uint64_t* last_term;   /* [G] raftLog.lastTerm()                      */
+  uint8_t* role;               /* [G] in/out: QB_ROLE_*                       */
+  uint32_t* election_elapsed;  /* [G] in/out */
+  uint32_t* heartbeat_elapsed; /* [G] in/out */
+} qb_follower_groups;
+
+/* M records in arrival order (SoA). */
+typedef struct qb_follower_inbox {
+  uint64_t M;            /* <= 2^32 - 2                                       */
+  const uint32_t* group; /* [M] */
+  const uint8_t* flags;  /* [M] QB_FIN_* in bits 0-2 | QB_FREC_FORCE          */
+  const uint64_t* from;  /* [M] sender ID                                     */
+  const uint64_t* term;  /* [M] Message.Term; 0 = local message               */
+  const uint64_t* index; /* [M] votes: Index; heartbeat: Commit               */
+  const uint64_t* aux;   /* [M] votes: LogTerm; heartbeat: the 8-byte context
+                          *     id (0 = empty), kept for the host             */
+} qb_follower_inbox;
+
+/* stats: QB_FSTAT_COUNT device uint64 (accumulated).  G == 0 or M == 0 is
+ * QB_OK; with M == 0 and G > 0 the per-group outputs are still initialised.
+ * No allocation inside the call (it can be graph-captured); nothing outside
+ * the caller's arrays is read or written. */
+size_t qb_follower_workspace_bytes(uint64_t G, uint64_t M);
+int qb_dev_follower_step(const qb_follower_groups* fg, const qb_follower_inbox* in,
+                         uint8_t* resp_type, uint64_t* resp_term, uint32_t* stop_at,
+                         uint8_t* gflags, uint64_t* stats, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
+/* ----------------------------------------------------------------------- */
 /* Wire ingest                                       */
 /* ----------------------------------------------------------------------- */
 

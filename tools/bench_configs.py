@@ -991,6 +991,180 @@ def tick_config(G, reps, *, reporter=None):
     assert ok, "tick parity failed"
 
 
+def follower_config(G, reps, *, reporter=None):
+    """The batched follower step (qb_dev_follower_step): G follower groups
+    (term 7, leader 1 known, CheckQuorum and PreVote on, ElectionTick 10).
+    Heartbeat sample: M = G same-term MsgHeartbeat, one per group in shuffled
+    arrival order, Commit one past the previous sample's (inside lastIndex), so
+    every group commits and answers; electionElapsed is put back to 1 between
+    samples (a tick passed), outside the timed call.  Storm sample: the lease
+    has run out (electionElapsed 10); M = 2 G records in shuffled order, per
+    group one MsgPreVote and then one MsgVote at term 8 from an up-to-date
+    candidate: both granted, the vote through becomeFollower; the state is
+    restored between samples, outside the timed call.  Parity at this size:
+    tests/follower_ref.py over the records of every 1024th group (4096
+    groups; exact, because groups are independent) — their state, responses,
+    gflags and stop_at after one call of each sample."""
+    reporter = reporter or report
+    import ctypes as C
+    from etcd_amd import _lib
+    from etcd_amd.quorum import follower as qf, tick as qt
+    from etcd_amd.quorum.leader import _to_np
+    from tests import follower_ref as F
+    ET, TERM = 10, 7
+    i64 = lambda v: torch.full((G,), v, dtype=torch.int64, device=dev)  # noqa: E731
+    g = torch.arange(G, dtype=torch.int64, device=dev)
+    base = 1000 + (g * 37) % 1000
+    t = {"term": i64(TERM), "vote": i64(1), "lead": i64(1), "committed": base.clone(),
+         "last_index": base + 4096, "last_term": i64(TERM)}
+    state = qt.TickState(torch.full((G,), qt.ROLE_PROMOTABLE, dtype=torch.uint8, device=dev),
+                         torch.ones(G, dtype=torch.int32, device=dev),
+                         torch.zeros(G, dtype=torch.int32, device=dev),
+                         torch.full((G,), 15, dtype=torch.int32, device=dev))
+    fg = qf.FollowerGroups(G, ET, True, True, t, state)
+    pristine = {k: v.clone() for k, v in t.items()}
+
+    def inbox_of(grp, flags, frm, term, index, aux):
+        ib = qf.FollowerInbox(grp.to(torch.int32), flags.to(torch.uint8), frm, term, index, aux)
+        ib._m = int(grp.numel())
+        return ib
+    # heartbeats: one per group, shuffled
+    hg = torch.randperm(G, device=dev)
+    hb = inbox_of(hg, torch.zeros_like(hg), torch.ones_like(hg), torch.full_like(hg, TERM),
+                  base[hg] + 1, torch.zeros_like(hg))
+    # storm: two per group, shuffled; the group's first is the MsgPreVote
+    sg = torch.randperm(2 * G, device=dev) % G
+    order = torch.argsort(sg, stable=True)
+    rank = torch.empty_like(order)
+    rank[order] = torch.arange(2 * G, device=dev) % 2
+    storm = inbox_of(sg, torch.where(rank == 0, qf.FIN_PREVOTE, qf.FIN_VOTE),
+                     torch.full_like(sg, 2), torch.full_like(sg, TERM + 1), (base + 4096)[sg],
+                     torch.full_like(sg, TERM))
+    res_hb = qf.follower_step(fg, hb)       # (the mirror's argument checks, once each)
+    res_st = qf.follower_step(fg, storm)
+    sp = torch.cuda.current_stream(dev).cuda_stream
+    fgc = qf.FollowerGroupsC(G=G, election_timeout=ET, check_quorum=1, pre_vote=1, reserved=0,
+                             role=state.role.data_ptr(),
+                             election_elapsed=state.election_elapsed.data_ptr(),
+                             heartbeat_elapsed=state.heartbeat_elapsed.data_ptr(),
+                             **{k: v.data_ptr() for k, v in t.items()})
+    fn = _lib.fn("qb_dev_follower_step")
+
+    def caller(ib, res):
+        ibc = qf.FollowerInboxC(M=ib.M, group=ib.group.data_ptr(), flags=ib.flags.data_ptr(),
+                                term=ib.term.data_ptr(), index=ib.index.data_ptr(),
+                                aux=ib.aux.data_ptr())
+        setattr(ibc, "from", ib.frm.data_ptr())
+        args = (C.byref(fgc), C.byref(ibc), res.resp_type.data_ptr(), res.resp_term.data_ptr(),
+                res.stop_at.data_ptr(), res.gflags.data_ptr(), res.stats.data_ptr(),
+                res.workspace.data_ptr(), res.workspace.numel() * 8, sp)
+        return lambda: _lib.check(fn(*args), "qb_dev_follower_step")
+    call_hb, call_st = caller(hb, res_hb), caller(storm, res_st)
+
+    def restore(ee):
+        for k, v in pristine.items():
+            t[k].copy_(v)
+        state.role.fill_(qt.ROLE_PROMOTABLE)
+        state.election_elapsed.fill_(ee)
+        state.heartbeat_elapsed.zero_()
+
+    def timed(call, prepare, n):
+        ev = HipEvents(2)
+        ts = []
+        for k in range(n):
+            prepare(k)
+            torch.cuda.synchronize()
+            ev.record(ev.ev[0], sp)
+            call()
+            ev.record(ev.ev[1], sp)
+            torch.cuda.synchronize()
+            ts.append(ev.elapsed_ms(0, 1) / 1e3)
+        ev.close()
+        return ts
+
+    def prep_hb(k):
+        if k % 4000 == 0:   # Commit stays inside lastIndex = base + 4096
+            restore(1)
+            hb.index.copy_(base[hg])
+        hb.index.add_(1)
+        state.election_elapsed.fill_(1)
+    timed(call_hb, prep_hb, 5)              # warm-up
+    res_hb.stats.zero_()
+    restore(1)
+    hb.index.copy_(base[hg])
+    t_hb = float(np.median(timed(call_hb, lambda k: prep_hb(k + 1), reps)))
+    st = res_hb.stats_dict()
+    assert st["heartbeats"] == reps * G and sum(st.values()) == reps * G, st
+    timed(call_st, lambda k: restore(ET), 5)
+    res_st.stats.zero_()
+    t_st = float(np.median(timed(call_st, lambda k: restore(ET), reps)))
+    st = res_st.stats_dict()
+    assert st["granted"] == 2 * reps * G and st["became_follower"] == reps * G, st
+    # algorithmic bytes.  Heartbeat, per record: group 4, flags 1, from 8, term
+    # 8, Commit 8 in, resp_type 1 + resp_term 8 out = 38; per group: term 8,
+    # lead 8, committed 8 in + 8 out, last_index 8, role 1, electionElapsed 4
+    # in + 4 out, gflags 1, stop_at 4 = 54.  Storm, per record: the heartbeat's
+    # 29 in + LogTerm 8, 9 out = 46, two per group; per group: term, vote and
+    # lead 8 in + 8 out each, last_index 8, last_term 8, role 1,
+    # electionElapsed 4 + 4, heartbeatElapsed 4 out, gflags 1, stop_at 4 = 82.
+    hb_b, st_b = 38 + 54, 2 * 46 + 82
+    extra = {"unit": "groups/s", "samples": reps, "records_per_group": 1,
+             "heartbeat_us": t_hb * 1e6, "heartbeat_bytes_per_group": hb_b,
+             "heartbeat_frac": G * hb_b / t_hb / 1e9 / HBM_PEAK_GBS,
+             "storm_us": t_st * 1e6, "storm_bytes_per_group": st_b, "storm_records": 2 * G,
+             "storm_frac": G * st_b / t_st / 1e9 / HBM_PEAK_GBS,
+             "election_tick": ET, "check_quorum": 1, "pre_vote": 1,
+             "timing": "one HIP event pair per call, median over the samples; state and "
+                       "counters restored outside the timed call"}
+
+    # parity at this size over every 1024th group
+    def parity(ib, call, res, ee, what):
+        restore(ee)
+        if ib is hb:
+            hb.index.copy_(base[hg] + 1)
+        res.stats.zero_()
+        torch.cuda.synchronize()
+        grp = _to_np(ib.group, np.uint32, ib.M)
+        sel = np.flatnonzero(grp % 1024 == 5)
+        sub = np.unique(grp[sel])
+        before = {k: _to_np(v, np.uint64, G)[sub].copy() for k, v in t.items()}
+        sb = {k: v[sub].copy() for k, v in state.numpy(G).items()}
+        cols = {k: _to_np(getattr(ib, k), dt, ib.M)[sel] for k, dt in (
+            ("flags", np.uint8), ("frm", np.uint64), ("term", np.uint64), ("index", np.uint64),
+            ("aux", np.uint64))}
+        call()
+        torch.cuda.synchronize()
+        nodes = [F.Node(*(int(before[k][j]) for k in ("term", "vote", "lead", "committed",
+                                                       "last_index", "last_term")),
+                        int(sb["role"][j]), int(sb["election_elapsed"][j]),
+                        int(sb["heartbeat_elapsed"][j])) for j in range(len(sub))]
+        where = {int(gg): j for j, gg in enumerate(sub)}
+        recs = [(where[int(grp[i])], F.Rec(int(cols["flags"][k]) & 7, int(cols["frm"][k]),
+                                           int(cols["term"][k]), int(cols["index"][k]),
+                                           int(cols["aux"][k]), bool(cols["flags"][k] & 0x80)))
+                for k, i in enumerate(sel)]
+        rt, rterm, stop, gf, _ = F.step_batch(nodes, recs, F.Config(ET, True, True))
+        stop = [int(sel[s]) if s != F.NO_STOP else s for s in stop]
+        after = fg.numpy()
+        ok = all(np.array_equal(after[k][sub], np.array([getattr(n, k) for n in nodes],
+                                                        after[k].dtype)) for k in after)
+        ok = (ok and np.array_equal(_to_np(res.resp_type, np.uint8, ib.M)[sel], np.array(rt, np.uint8))
+              and np.array_equal(_to_np(res.resp_term, np.uint64, ib.M)[sel],
+                                 np.array(rterm, np.uint64))
+              and np.array_equal(_to_np(res.stop_at, np.uint32, G)[sub], np.array(stop, np.uint32))
+              and np.array_equal(_to_np(res.gflags, np.uint8, G)[sub], np.array(gf, np.uint8)))
+        extra[f"parity_{what}"] = bool(ok)
+        return ok, len(sub), len(sel)
+    ok_h, ng, nr_h = parity(hb, call_hb, res_hb, 1, "heartbeat")
+    ok_s, _, nr_s = parity(storm, call_st, res_st, ET, "storm")
+    extra["parity"] = bool(ok_h and ok_s)
+    extra["parity_check"] = (f"tests/follower_ref.py over the records of {ng} groups (every 1024th) "
+                             f"of the {G}: {nr_h} heartbeat / {nr_s} storm records; state, "
+                             "resp_type, resp_term, stop_at and gflags")
+    reporter("follower step (heartbeats; pre-vote + vote storm)", G, t_hb, G * hb_b, extra)
+    assert ok_h and ok_s, "follower parity failed"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -1030,6 +1204,8 @@ def main():
         confchange_config(1 << 23, a.reps)
     if "tick" in which:
         tick_config(1 << 22, a.reps)
+    if "follower" in which:
+        follower_config(1 << 22, a.reps)
     if "wire-tracker" in which:
         wire_tracker_config(1 << 24, a.reps)
     if "wire-tracker-fused" in which:  # development A/B: the one call alone
