@@ -18,13 +18,11 @@ import torch
 import torch.distributed as dist
 
 from etcd_amd import _lib
+from etcd_amd.quorum._dev import grow_workspace
+from etcd_amd.quorum._dev import stream_handle as _stream
 
 QB_COMM_ID_BYTES = 128
 _ROUTE_COLS = ("group", "flags", "index", "term", "hint", "log_term")
-
-
-def _stream(dev) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 class RcclComm:
@@ -119,8 +117,7 @@ class RcclComm:
         return None
 
     def _workspace(self, nbytes: int) -> torch.Tensor:
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
+        self._ws = grow_workspace(self._ws, nbytes, self.device)
         return self._ws
 
     def allgather_results(self, commit: torch.Tensor, vote: torch.Tensor, total: int,

@@ -5,7 +5,6 @@
 #pragma once
 
 #include "qb_common.h"
-#include "qb_scan.h"
 
 namespace qb {
 namespace bk {
@@ -318,8 +317,8 @@ inline Geometry geometry(u32 n, u64 G, u64 M, u32 ch = 0, bool il = false) {
   // at most what the region's tiles can hold (and never more than the batch)
   u64 worst = tps * kTile;
   worst = worst < M ? worst : M;
-  u64 cap = (2 * m + 256 + 255) / 256 * 256;  // (256-record granules)
-  cap = cap < worst ? cap : (worst + 255) / 256 * 256;
+  u64 cap = up256(2 * m + 256);  // (256-record granules)
+  cap = cap < worst ? cap : up256(worst);
   const u64 capmax = kMaxRows / S * kTile;  // the run table's rows per super-bucket
   cap = cap < 256 ? 256 : cap > capmax ? capmax : cap;
   g.cap = u32(cap);
@@ -344,7 +343,6 @@ struct Carve {
   u64 nrec;    // records of the region grid (pool part 0 starts here)
   u64 nrec_all;  // records per column of buf1 / buf2: the region grid + the pool
 };
-inline size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
 // ncols = 3: the wide form (index, term32, mr; the leader step); ncols = 1:
 // the compact form, whose u8 chunk-low column rides in the carve's cl area
 // (the tracker steps).  user: bytes of the caller's own (at `user`) zeroed

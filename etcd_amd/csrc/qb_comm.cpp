@@ -49,7 +49,76 @@ uint64_t shard_cap(uint64_t total, int world) {
   return (total + uint64_t(world) - 1) / uint64_t(world);
 }
 
-size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
+using qb::Carver;
+
+// qb_dev_allgather_results: the padded send shard (commit then vote, cap
+// entries each), the receive vectors (world * cap each) and one spare piece.
+struct GatherCarve {
+  uint64_t cap;
+  size_t send_c, send_v, recv_c, recv_v, total;
+};
+GatherCarve gather_carve(uint64_t total, int world) {
+  GatherCarve c{};
+  Carver k;
+  c.cap = shard_cap(total, world);
+  c.send_c = k.take(9 * c.cap);
+  c.send_v = c.send_c + 8 * c.cap;
+  c.recv_c = k.take(9 * c.cap * uint64_t(world));
+  c.recv_v = c.recv_c + 8 * c.cap * uint64_t(world);
+  c.total = k.o + 256;
+  return c;
+}
+
+// qb_dev_allgather_changed: the compaction's workspace, this rank's pairs,
+// its count, the gathered counts (two pieces) and the gathered pairs.
+struct ChangedCarve {
+  uint64_t cap;
+  size_t compact_bytes;  // qb_compact_changed_workspace_bytes(cap)
+  size_t compact, gid, val, count, counts, gid_all, val_all, total;
+};
+ChangedCarve changed_carve(uint64_t total, int world) {
+  ChangedCarve c{};
+  Carver k;
+  c.cap = shard_cap(total, world);
+  c.compact_bytes = qb_compact_changed_workspace_bytes(c.cap);
+  c.compact = k.take(c.compact_bytes);
+  c.gid = k.take(4 * c.cap);
+  c.val = k.take(8 * c.cap);
+  c.count = k.take(256);
+  c.counts = k.take(sizeof(uint64_t) * size_t(world));
+  (void)k.take(sizeof(uint64_t) * size_t(world));  // (unused; the size counts it)
+  c.gid_all = k.take(4 * c.cap * uint64_t(world));
+  c.val_all = k.take(8 * c.cap * uint64_t(world));
+  c.total = k.o;
+  return c;
+}
+
+// qb_dev_route_records: the send columns (group 4, flags 1, index / term /
+// hint / log_term 8 bytes a record), the partition's workspace, send_off and
+// the count rows (a row: W counts, output capacity, ok flag), own and gathered.
+struct RouteCarve {
+  size_t part_bytes;  // qb_route_partition_workspace_bytes(world, M)
+  size_t row_words;   // u64 per row
+  size_t group, flags, index, term, hint, log_term, part, send_off, row, rows, total;
+};
+RouteCarve route_carve(int world, uint64_t M) {
+  RouteCarve c{};
+  Carver k;
+  c.part_bytes = qb_route_partition_workspace_bytes(world, M);
+  c.row_words = size_t(world) + 2;
+  c.group = k.take(4 * M);
+  c.flags = k.take(M);
+  c.index = k.take(8 * M);
+  c.term = k.take(8 * M);
+  c.hint = k.take(8 * M);
+  c.log_term = k.take(8 * M);
+  c.part = k.take(c.part_bytes);
+  c.send_off = k.take(sizeof(uint32_t) * (size_t(world) + 1));
+  c.row = k.take(sizeof(uint64_t) * size_t(world) * c.row_words);
+  c.rows = k.take(sizeof(uint64_t) * size_t(world) * c.row_words);
+  c.total = k.o;
+  return c;
+}
 
 }  // namespace
 
@@ -97,9 +166,7 @@ extern "C" int qb_comm_destroy(qb_comm* c) {
 
 extern "C" size_t qb_allgather_workspace_bytes(uint64_t total, int world) {
   if (world < 1) return 0;
-  const uint64_t cap = shard_cap(total, world);
-  // padded send (cap) + receive (world * cap) for both vectors
-  return up256(9 * cap) + up256(9 * cap * uint64_t(world)) + 256;
+  return gather_carve(total, world).total;
 }
 
 extern "C" int qb_dev_allgather_results(qb_comm* c, uint64_t total,
@@ -111,7 +178,8 @@ extern "C" int qb_dev_allgather_results(qb_comm* c, uint64_t total,
   if (total == 0) return QB_OK;
   hipStream_t st = qb::as_stream(stream);
   const int W = c->world;
-  const uint64_t cap = shard_cap(total, W);
+  const GatherCarve cv = gather_carve(total, W);
+  const uint64_t cap = cv.cap;
   uint64_t b = 0, e = 0;
   shard_range(total, W, c->rank, &b, &e);
   const uint64_t mine = e - b;
@@ -127,12 +195,12 @@ extern "C" int qb_dev_allgather_results(qb_comm* c, uint64_t total,
   uint64_t* recv_c = commit_all;
   uint8_t* recv_v = vote_all;
   if (!even) {
-    QB_REQUIRE(ws && workspace_bytes >= qb_allgather_workspace_bytes(total, W),
+    QB_REQUIRE(ws && workspace_bytes >= cv.total,
                "workspace too small (qb_allgather_workspace_bytes)");
-    send_c = reinterpret_cast<uint64_t*>(ws);
-    send_v = reinterpret_cast<uint8_t*>(ws + 8 * cap);
-    recv_c = reinterpret_cast<uint64_t*>(ws + up256(9 * cap));
-    recv_v = reinterpret_cast<uint8_t*>(ws + up256(9 * cap) + 8 * cap * uint64_t(W));
+    send_c = reinterpret_cast<uint64_t*>(ws + cv.send_c);
+    send_v = reinterpret_cast<uint8_t*>(ws + cv.send_v);
+    recv_c = reinterpret_cast<uint64_t*>(ws + cv.recv_c);
+    recv_v = reinterpret_cast<uint8_t*>(ws + cv.recv_v);
     hipError_t h = hipSuccess;
     if (commit_all) h = hipMemcpyAsync(send_c, commit_shard, 8 * mine, hipMemcpyDeviceToDevice, st);
     if (h == hipSuccess && vote_all)
@@ -177,10 +245,7 @@ extern "C" int qb_dev_allgather_results(qb_comm* c, uint64_t total,
 // (its own included) to commit_all, which the caller keeps across ticks.
 extern "C" size_t qb_allgather_changed_workspace_bytes(uint64_t total, int world) {
   if (world < 1) return 0;
-  const uint64_t cap = shard_cap(total, world);
-  return qb_compact_changed_workspace_bytes(cap) + up256(4 * cap) + up256(8 * cap) + 256 +
-         2 * up256(sizeof(uint64_t) * size_t(world)) + up256(4 * cap * uint64_t(world)) +
-         up256(8 * cap * uint64_t(world));
+  return changed_carve(total, world).total;
 }
 
 extern "C" int qb_dev_allgather_changed(qb_comm* c, uint64_t total, const uint8_t* changed_shard,
@@ -191,32 +256,26 @@ extern "C" int qb_dev_allgather_changed(qb_comm* c, uint64_t total, const uint8_
   QB_REQUIRE(commit_all, "commit_all NULL");
   QB_REQUIRE(total <= 0xFFFFFFFFull, "total must fit uint32 (%llu)", (unsigned long long)total);
   const int W = c->world;
-  QB_REQUIRE(workspace && workspace_bytes >= qb_allgather_changed_workspace_bytes(total, W),
+  const ChangedCarve cv = changed_carve(total, W);
+  QB_REQUIRE(workspace && workspace_bytes >= cv.total,
              "workspace too small (qb_allgather_changed_workspace_bytes)");
   *changed_total = 0;
   hipStream_t st = qb::as_stream(stream);
   uint64_t b = 0, e = 0;
   shard_range(total, W, c->rank, &b, &e);
-  const uint64_t n = e - b, cap = shard_cap(total, W);
+  const uint64_t n = e - b, cap = cv.cap;
   // (NULL shard columns are not checked here: qb_dev_compact_changed refuses
   // them and the refusal travels to every rank as a ~0 count below — an early
   // return here would leave the other ranks waiting in the count all-gather)
   char* ws = static_cast<char*>(workspace);
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    char* p = ws + o;
-    o += up256(bytes);
-    return p;
-  };
-  const size_t cws = qb_compact_changed_workspace_bytes(cap);
-  void* cw = take(cws);
-  uint32_t* gid = reinterpret_cast<uint32_t*>(take(4 * cap));
-  uint64_t* val = reinterpret_cast<uint64_t*>(take(8 * cap));
-  uint64_t* count = reinterpret_cast<uint64_t*>(take(256));
-  uint64_t* counts = reinterpret_cast<uint64_t*>(take(sizeof(uint64_t) * size_t(W)));
-  (void)take(sizeof(uint64_t) * size_t(W));
-  uint32_t* gid_all = reinterpret_cast<uint32_t*>(take(4 * cap * uint64_t(W)));
-  uint64_t* val_all = reinterpret_cast<uint64_t*>(take(8 * cap * uint64_t(W)));
+  const size_t cws = cv.compact_bytes;
+  void* cw = ws + cv.compact;
+  uint32_t* gid = reinterpret_cast<uint32_t*>(ws + cv.gid);
+  uint64_t* val = reinterpret_cast<uint64_t*>(ws + cv.val);
+  uint64_t* count = reinterpret_cast<uint64_t*>(ws + cv.count);
+  uint64_t* counts = reinterpret_cast<uint64_t*>(ws + cv.counts);
+  uint32_t* gid_all = reinterpret_cast<uint32_t*>(ws + cv.gid_all);
+  uint64_t* val_all = reinterpret_cast<uint64_t*>(ws + cv.val_all);
   // a local failure travels as count ~0 in the gathered counts, so every rank
   // returns together instead of some waiting in the exchange
   const int rc = qb_dev_compact_changed(n, changed_shard, commit_shard, b, gid, val, count, cw,
@@ -290,11 +349,7 @@ extern "C" int qb_dev_allgather_changed(qb_comm* c, uint64_t total, const uint8_
 // counts (the receive sizes are data-dependent).
 extern "C" size_t qb_route_workspace_bytes(int world, uint64_t M) {
   if (world < 1 || world > QB_ROUTE_MAX_WORLD) return 0;
-  // send columns (group 4, flags 1, index/term/hint/log_term 32) + the
-  // partition's workspace + send_off and the all-gathered rows
-  return up256(4 * M) + up256(M) + 4 * up256(8 * M) + qb_route_partition_workspace_bytes(world, M) +
-         up256(sizeof(uint32_t) * (size_t(world) + 1)) +
-         2 * up256(sizeof(uint64_t) * size_t(world) * size_t(world + 2));
+  return route_carve(world, M).total;
 }
 
 extern "C" int qb_dev_route_records(qb_comm* c, uint64_t total, uint64_t M,
@@ -313,29 +368,24 @@ extern "C" int qb_dev_route_records(qb_comm* c, uint64_t total, uint64_t M,
   QB_REQUIRE(c && out_count, "comm / out_count NULL");
   const int W = c->world;
   QB_REQUIRE(W <= QB_ROUTE_MAX_WORLD, "world %d > %d", W, QB_ROUTE_MAX_WORLD);
-  QB_REQUIRE(workspace && workspace_bytes >= qb_route_workspace_bytes(W, M),
+  const RouteCarve cv = route_carve(W, M);
+  QB_REQUIRE(workspace && workspace_bytes >= cv.total,
              "workspace too small (qb_route_workspace_bytes)");
   *out_count = 0;
   hipStream_t st = qb::as_stream(stream);
   char* ws = static_cast<char*>(workspace);
-  size_t o = 0;
-  auto take = [&](size_t n) {
-    char* p = ws + o;
-    o += up256(n);
-    return p;
-  };
-  uint32_t* s_group = reinterpret_cast<uint32_t*>(take(4 * M));
-  uint8_t* s_flags = reinterpret_cast<uint8_t*>(take(M));
-  uint64_t* s_index = reinterpret_cast<uint64_t*>(take(8 * M));
-  uint64_t* s_term = reinterpret_cast<uint64_t*>(take(8 * M));
-  uint64_t* s_hint = reinterpret_cast<uint64_t*>(take(8 * M));
-  uint64_t* s_lt = reinterpret_cast<uint64_t*>(take(8 * M));
-  const size_t pws = qb_route_partition_workspace_bytes(W, M);
-  void* part_ws = take(pws);
-  uint32_t* send_off = reinterpret_cast<uint32_t*>(take(sizeof(uint32_t) * (size_t(W) + 1)));
-  const size_t RW = size_t(W) + 2;  // a row: W counts, output capacity, ok flag
-  uint64_t* row = reinterpret_cast<uint64_t*>(take(sizeof(uint64_t) * size_t(W) * RW));
-  uint64_t* rows = reinterpret_cast<uint64_t*>(take(sizeof(uint64_t) * size_t(W) * RW));
+  uint32_t* s_group = reinterpret_cast<uint32_t*>(ws + cv.group);
+  uint8_t* s_flags = reinterpret_cast<uint8_t*>(ws + cv.flags);
+  uint64_t* s_index = reinterpret_cast<uint64_t*>(ws + cv.index);
+  uint64_t* s_term = reinterpret_cast<uint64_t*>(ws + cv.term);
+  uint64_t* s_hint = reinterpret_cast<uint64_t*>(ws + cv.hint);
+  uint64_t* s_lt = reinterpret_cast<uint64_t*>(ws + cv.log_term);
+  const size_t pws = cv.part_bytes;
+  void* part_ws = ws + cv.part;
+  uint32_t* send_off = reinterpret_cast<uint32_t*>(ws + cv.send_off);
+  const size_t RW = cv.row_words;  // a row: W counts, output capacity, ok flag
+  uint64_t* row = reinterpret_cast<uint64_t*>(ws + cv.row);
+  uint64_t* rows = reinterpret_cast<uint64_t*>(ws + cv.rows);
   std::string local_err;
   int local_rc = QB_OK;
   if (!rec_hint != !out_hint || !rec_log_term != !out_log_term) {

@@ -103,6 +103,32 @@ __host__ __device__ __forceinline__ u8 joint_vote(u8 r1, u8 r2) {
   return QB_VOTE_PENDING;
 }
 
+// JointConfig.VoteResult (joint.go:61-75) over slot masks: the incoming and
+// the outgoing half each tallied by majority.go:178-210, then joined.
+__host__ __device__ __forceinline__ u8 masks_vote(u32 min_, u32 mout, u32 granted, u32 voted) {
+  const u8 r1 = vote_from_counts(__builtin_popcount(min_), __builtin_popcount(min_ & granted),
+                                 __builtin_popcount(min_ & voted));
+  const u8 r2 = vote_from_counts(__builtin_popcount(mout), __builtin_popcount(mout & granted),
+                                 __builtin_popcount(mout & voted));
+  return joint_vote(r1, r2);
+}
+
+// ProgressTracker.QuorumActive (tracker.go:215-225) over the slot masks of a
+// cfg word (incoming low half, outgoing high half): every voter has a
+// Progress, so each has "voted" its RecentActive.
+__host__ __device__ __forceinline__ bool quorum_active(u32 cfg, u32 active) {
+  return masks_vote(cfg & 0xFFFFu, cfg >> 16, active, ~0u) == QB_VOTE_WON;
+}
+
+// ------------------------------------------------------------ workspaces ---
+// Every workspace is carved into 256-byte aligned pieces.  A layout function
+// fills a struct of offsets with Carver::take and ends with total = o.
+inline size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
+struct Carver {
+  size_t o = 0;
+  size_t take(size_t bytes) { const size_t at = o; o += up256(bytes); return at; }
+};
+
 // ------------------------------------------------------------- counters ---
 // Statistics are tallied per wave (a wave-uniform popcount of a ballot, kept
 // in a register), reduced per block in LDS, and flushed with ONE global

@@ -706,13 +706,23 @@ __global__ __launch_bounds__(256) void k_cc_move(Args A) {
 using namespace qb;
 
 namespace {
-// the scan's block sums, the any_big word, the slot codes
-size_t cc_codes_at(uint64_t G) { return ((scan::blocks(G) + 1) * sizeof(u32) + 255) / 256 * 256 + 256; }
+// Workspace: the scan's block sums, the any_big word, the slot codes (not
+// rounded up) and one spare piece.
+struct Carve {
+  size_t bsum, any_big, codes, total;
+};
+Carve carve(u64 G) {
+  Carve c{};
+  Carver k;
+  c.bsum = k.take(sizeof(u32) * (scan::blocks(G) + 1));
+  c.any_big = k.take(sizeof(u32));
+  c.codes = k.o;
+  c.total = c.codes + sizeof(u64) * G + 256;
+  return c;
+}
 }  // namespace
 
-extern "C" size_t qb_conf_change_workspace_bytes(uint64_t G) {
-  return cc_codes_at(G) + G * sizeof(u64) + 256;
-}
+extern "C" size_t qb_conf_change_workspace_bytes(uint64_t G) { return carve(G).total; }
 
 extern "C" int qb_dev_conf_change(const qb_conf_change_in* in, const qb_conf_change_out* out,
                                   void* workspace, size_t workspace_bytes, void* stream) {
@@ -729,8 +739,8 @@ extern "C" int qb_dev_conf_change(const qb_conf_change_in* in, const qb_conf_cha
                  out->pending_snapshot && out->pstate && out->infl_pos && out->err &&
                  (in->inflight_cap == 0 || out->infl_buf),
              "qb_dev_conf_change: every output array is required");
-  QB_REQUIRE(workspace && workspace_bytes >= qb_conf_change_workspace_bytes(G),
-             "qb_dev_conf_change: workspace too small");
+  const Carve cv = carve(G);
+  QB_REQUIRE(workspace && workspace_bytes >= cv.total, "qb_dev_conf_change: workspace too small");
   cc::Args A{};
   A.G = G;
   A.op = in->op;
@@ -765,9 +775,9 @@ extern "C" int qb_dev_conf_change(const qb_conf_change_in* in, const qb_conf_cha
   A.err = out->err;
   A.err_id = reinterpret_cast<u64*>(out->err_id);
   hipStream_t st = as_stream(stream);
-  const size_t scan_bytes = (scan::blocks(G) + 1) * sizeof(u32);
-  A.any_big = reinterpret_cast<u32*>(static_cast<char*>(workspace) + (scan_bytes + 255) / 256 * 256);
-  A.codes = reinterpret_cast<u64*>(static_cast<char*>(workspace) + cc_codes_at(G));
+  char* ws = static_cast<char*>(workspace);
+  A.any_big = reinterpret_cast<u32*>(ws + cv.any_big);
+  A.codes = reinterpret_cast<u64*>(ws + cv.codes);
   {
     const hipError_t e = hipMemsetAsync(A.any_big, 0, sizeof(u32), st);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(any_big)");
@@ -777,13 +787,10 @@ extern "C" int qb_dev_conf_change(const qb_conf_change_in* in, const qb_conf_cha
   hipLaunchKernelGGL((cc::k_cc_count<cc::kSmall, false>), dim3(grid), dim3(cc::kBlk), 0, st, A);
   hipLaunchKernelGGL((cc::k_cc_count<cc::kTab, true>), dim3(big_grid), dim3(cc::kBlk), 0, st, A);
   QB_CHECK_LAUNCH("k_cc_count");
-  {  // local scan + block sums (the add-back is in k_cc_write); new_off[G] = total
-    u32* bsum = static_cast<u32*>(workspace);
-    const u32 nb = scan::blocks(G);
-    hipLaunchKernelGGL(scan::k_scan_local, dim3(nb), dim3(1024), 0, st, out->new_off, G, bsum);
-    hipLaunchKernelGGL(scan::k_scan_sums, dim3(1), dim3(1024), 0, st, bsum, nb, out->new_off + G);
-    A.nbsum = bsum;
-  }
+  // local scan + block sums (the add-back is in k_cc_write); new_off[G] = total
+  u32* bsum = reinterpret_cast<u32*>(ws + cv.bsum);
+  scan::launch_partial(out->new_off, G, bsum, out->new_off + G, st);
+  A.nbsum = bsum;
   QB_CHECK_LAUNCH("scan(conf change)");
   hipLaunchKernelGGL(cc::k_cc_write<cc::kTab>, dim3(big_grid), dim3(cc::kBlk), 0, st, A);
   QB_CHECK_LAUNCH("k_cc_write");

@@ -100,11 +100,24 @@ __global__ __launch_bounds__(kBlock) void k_delta_write(u64 n, const u8* __restr
 
 using namespace qb;
 
-extern "C" size_t qb_compact_changed_workspace_bytes(uint64_t n) {
-  const u64 nt = (n + delta::kTile - 1) / delta::kTile;
-  return (sizeof(u32) * (nt + 1) + 255) / 256 * 256 +
-         (sizeof(u32) * (scan::blocks(nt) + 1) + 255) / 256 * 256 + 256;
+namespace {
+// Workspace: the tile counts, their scan's block sums and one spare piece.
+struct Carve {
+  u64 nt;  // tiles
+  size_t cnt, bsum, total;
+};
+Carve carve(u64 n) {
+  Carve c{};
+  Carver k;
+  c.nt = (n + delta::kTile - 1) / delta::kTile;
+  c.cnt = k.take(sizeof(u32) * (c.nt + 1));
+  c.bsum = k.take(sizeof(u32) * (scan::blocks(c.nt) + 1));
+  c.total = k.o + 256;
+  return c;
 }
+}  // namespace
+
+extern "C" size_t qb_compact_changed_workspace_bytes(uint64_t n) { return carve(n).total; }
 
 extern "C" int qb_dev_compact_changed(uint64_t n, const uint8_t* changed, const uint64_t* commit,
                                       uint64_t g_base, uint32_t* out_gid, uint64_t* out_commit,
@@ -114,17 +127,18 @@ extern "C" int qb_dev_compact_changed(uint64_t n, const uint8_t* changed, const 
   QB_REQUIRE(n == 0 || (changed && commit && out_gid && out_commit), "NULL column");
   QB_REQUIRE(g_base + n <= 0xFFFFFFFFull, "global groups must fit uint32 (g_base + n = %llu)",
              (unsigned long long)(g_base + n));
-  QB_REQUIRE(workspace && workspace_bytes >= qb_compact_changed_workspace_bytes(n),
+  const Carve cv = carve(n);
+  QB_REQUIRE(workspace && workspace_bytes >= cv.total,
              "workspace too small (qb_compact_changed_workspace_bytes)");
   hipStream_t st = as_stream(stream);
   if (n == 0) {
     const hipError_t e = hipMemsetAsync(out_count, 0, sizeof(u64), st);
     return e == hipSuccess ? QB_OK : hip_fail(e, "hipMemsetAsync(count)");
   }
-  const u32 nt = u32((n + delta::kTile - 1) / delta::kTile);
+  const u32 nt = u32(cv.nt);
   char* ws = static_cast<char*>(workspace);
-  u32* cnt = reinterpret_cast<u32*>(ws);
-  u32* bsum = reinterpret_cast<u32*>(ws + (sizeof(u32) * (u64(nt) + 1) + 255) / 256 * 256);
+  u32* cnt = reinterpret_cast<u32*>(ws + cv.cnt);
+  u32* bsum = reinterpret_cast<u32*>(ws + cv.bsum);
   hipLaunchKernelGGL(delta::k_delta_count, dim3(nt), dim3(kBlock), 0, st, n, changed, cnt);
   QB_CHECK_LAUNCH("k_delta_count");
   scan::launch(cnt, nt, bsum, st);

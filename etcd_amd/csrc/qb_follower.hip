@@ -358,17 +358,16 @@ __global__ __launch_bounds__(kBlock) void k_long(Args A) {
 struct Carve {
   size_t cnt, nlong, zero_end, bsum, longs, perm, total;
 };
-inline size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
 inline Carve carve(u64 G, u64 M) {
   Carve c{};
-  size_t o = 0;
-  c.cnt = o;  o += up256(sizeof(u32) * (G + 1));
-  c.nlong = o;  o += 256;
-  c.zero_end = o;
-  c.bsum = o;  o += up256(sizeof(u32) * (u64(scan::blocks(G)) + 1));
-  c.longs = o;  o += up256(sizeof(u32) * (M / (kInline + 1) + 1));
-  c.perm = o;  o += up256(sizeof(u32) * (M ? M : 1));
-  c.total = o;
+  Carver k;
+  c.cnt = k.take(sizeof(u32) * (G + 1));
+  c.nlong = k.take(256);
+  c.zero_end = k.o;
+  c.bsum = k.take(sizeof(u32) * (u64(scan::blocks(G)) + 1));
+  c.longs = k.take(sizeof(u32) * (M / (kInline + 1) + 1));
+  c.perm = k.take(sizeof(u32) * (M ? M : 1));
+  c.total = k.o;
   return c;
 }
 

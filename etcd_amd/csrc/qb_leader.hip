@@ -66,8 +66,6 @@ struct ReadSt {
 };
 static_assert(sizeof(ReadSt) == sizeof(qb_read_state), "qb_read_state layout");
 
-inline size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
-
 // The ABI's uint64_t is unsigned long; HIP atomics and qb helpers use u64.
 __host__ __device__ __forceinline__ u64* U(uint64_t* p) { return reinterpret_cast<u64*>(p); }
 __host__ __device__ __forceinline__ const u64* U(const uint64_t* p) {
@@ -942,13 +940,9 @@ __device__ void bcast_append(const Args& A, Group& G_) {
     if (s != leader_slot(G_)) maybe_send_append<S>(A, G_, s, true);
 }
 
-// joint.go:61-75 over majority.go:178-210 with votes = acks (all true).
+// masks_vote with votes = acks (all true).
 __device__ __forceinline__ u8 acks_vote(const Group& G_, u32 acks) {
-  const u8 r1 = vote_from_counts(__popc(G_.mask_in), __popc(G_.mask_in & acks),
-                                 __popc(G_.mask_in & acks));
-  const u8 r2 = vote_from_counts(__popc(G_.mask_out), __popc(G_.mask_out & acks),
-                                 __popc(G_.mask_out & acks));
-  return joint_vote(r1, r2);
+  return masks_vote(G_.mask_in, G_.mask_out, acks, acks);
 }
 
 template <bool S>
@@ -1506,9 +1500,7 @@ int leader_step_impl(const qb_leader_groups* lg, const qb_leader_inbox* in, cons
     u32* mbsum = reinterpret_cast<u32*>(ws + c.mbsum);
     // a local scan of the totals + the block sums' scan (the add-back is in
     // k_ld_emit); mbs[nblk] = all messages
-    const u32 nsb = scan::blocks(nblk);
-    hipLaunchKernelGGL(scan::k_scan_local, dim3(nsb), dim3(1024), 0, st, A.mbs, u64(nblk), mbsum);
-    hipLaunchKernelGGL(scan::k_scan_sums, dim3(1), dim3(1024), 0, st, mbsum, nsb, A.mbs + nblk);
+    scan::launch_partial(A.mbs, u64(nblk), mbsum, A.mbs + nblk, st);
     QB_CHECK_LAUNCH("scan(message totals)");
     hipLaunchKernelGGL(ld::k_ld_emit, dim3(grid_for(G)), dim3(kBlock), 0, st, G, sink->count, A.mbs,
                        mbsum, nblk, A.fix, A.chead, A.cnext, A.chunks,

@@ -393,9 +393,7 @@ __global__ __launch_bounds__(kBlock) void k_csr(u64 G, const u32* __restrict__ o
   if constexpr (VOTE) {
     if (live) {
       const u32 vd = w & 0xFFFFu, gr = (w >> 16) & vd;
-      const u8 r1 = vote_from_counts(__popc(min_), __popc(min_ & gr), __popc(min_ & vd));
-      const u8 r2 = vote_from_counts(__popc(mout), __popc(mout & gr), __popc(mout & vd));
-      vote[g] = joint_vote(r1, r2);
+      vote[g] = masks_vote(min_, mout, gr, vd);
     }
   }
 }

@@ -149,15 +149,27 @@ __global__ __launch_bounds__(kBlock) void k_route_scatter(Owner ow, u64 M, Cols 
 using namespace qb;
 
 namespace {
-size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
-u32 route_tiles(u64 M) { return u32((M + route::kTile - 1) / route::kTile); }
+// Workspace: the owner-major count matrix (+ its scan's block sums).
+struct Carve {
+  u32 nt;  // tiles
+  u64 n;   // counts: world x nt
+  size_t cnt, bsum, total;
+};
+Carve carve(int world, u64 M) {
+  Carve c{};
+  Carver k;
+  c.nt = u32((M + route::kTile - 1) / route::kTile);
+  c.n = u64(world) * c.nt;
+  c.cnt = k.take(sizeof(u32) * (c.n + 1));
+  c.bsum = k.take(sizeof(u32) * (scan::blocks(c.n) + 1));
+  c.total = k.o;
+  return c;
+}
 }  // namespace
 
-// Workspace: the owner-major count matrix (+ its scan's block sums).
 extern "C" size_t qb_route_partition_workspace_bytes(int world, uint64_t M) {
   if (world < 1 || world > QB_ROUTE_MAX_WORLD) return 0;
-  const u64 n = u64(world) * route_tiles(M);
-  return up256(sizeof(u32) * (n + 1)) + up256(sizeof(u32) * (scan::blocks(n) + 1));
+  return carve(world, M).total;
 }
 
 extern "C" int qb_dev_route_partition(uint64_t total, int world, uint64_t M,
@@ -181,13 +193,14 @@ extern "C" int qb_dev_route_partition(uint64_t total, int world, uint64_t M,
   }
   QB_REQUIRE(rec_group && rec_flags && rec_index && rec_term, "record column is NULL");
   QB_REQUIRE(send_group && send_flags && send_index && send_term, "send column is NULL");
-  QB_REQUIRE(workspace && workspace_bytes >= qb_route_partition_workspace_bytes(world, M),
+  const Carve cv = carve(world, M);
+  QB_REQUIRE(workspace && workspace_bytes >= cv.total,
              "workspace too small (qb_route_partition_workspace_bytes)");
-  const u32 nt = route_tiles(M);
-  const u64 n = u64(world) * nt;
+  const u32 nt = cv.nt;
+  const u64 n = cv.n;
   char* ws = static_cast<char*>(workspace);
-  u32* cnt = reinterpret_cast<u32*>(ws);
-  u32* bsum = reinterpret_cast<u32*>(ws + up256(sizeof(u32) * (n + 1)));
+  u32* cnt = reinterpret_cast<u32*>(ws + cv.cnt);
+  u32* bsum = reinterpret_cast<u32*>(ws + cv.bsum);
   const route::Owner ow = route::owner_of(total, u32(world));
   hipLaunchKernelGGL(route::k_route_count, dim3(nt), dim3(kBlock), 0, st, ow, M, rec_group, cnt, nt);
   QB_CHECK_LAUNCH("k_route_count");

@@ -67,15 +67,6 @@ struct Tile {
   u32 tally[QB_TSTAT_COUNT];
 };
 
-// ProgressTracker.QuorumActive (tracker.go:215-225) over the slot masks, the
-// rule of qb_dev_csr_quorum_active: every voter has "voted" its RecentActive.
-__device__ __forceinline__ bool quorum_active(u32 cfg, u32 active) {
-  const u32 min_ = cfg & 0xFFFFu, mout = cfg >> 16;
-  const u8 r1 = vote_from_counts(__popc(min_), __popc(min_ & active), __popc(min_));
-  const u8 r2 = vote_from_counts(__popc(mout), __popc(mout & active), __popc(mout));
-  return joint_vote(r1, r2) == QB_VOTE_WON;
-}
-
 __global__ __launch_bounds__(kBlock) void k_tick(Args A) {
   __shared__ Tile T;
   const qb_tick_groups& tg = A.tg;

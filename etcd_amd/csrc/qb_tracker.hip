@@ -15,15 +15,9 @@ namespace qb {
 
 // ------------------------------------------------------------ QuorumActive --
 
-// Every voter has a Progress, so votes[id] = RecentActive is present for
-// each: yes = popcount(mask & active), voted = n (tracker.go:216-222).
-__device__ __forceinline__ u8 quorum_active_one(u32 c, u32 a) {
-  const u32 min_ = c & 0xFFFFu, mout = c >> 16;
-  const u8 r1 = vote_from_counts(__popc(min_), __popc(min_ & a), __popc(min_));
-  const u8 r2 = vote_from_counts(__popc(mout), __popc(mout & a), __popc(mout));
-  return joint_vote(r1, r2) == QB_VOTE_WON ? 1 : 0;
-}
-
+// The rule is quorum_active (qb_common.h): yes = popcount(mask & active),
+// voted = n (tracker.go:216-222).
+//
 // kQaGpt groups per thread: two 16-byte cfg loads, one 16-byte active load
 // and one 8-byte store, all nontemporal (7 B/group streamed once); the
 // thread-per-group form moved 1-4 bytes per lane and reached 4.2 TB/s.
@@ -48,7 +42,7 @@ __global__ __launch_bounds__(kBlock) void k_quorum_active(u64 G, const u32* __re
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const u32 ak = (a[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu;
-      w[k >> 2] |= u32(quorum_active_one(c[k], ak)) << ((k & 3) * 8);
+      w[k >> 2] |= u32(quorum_active(c[k], ak)) << ((k & 3) * 8);
     }
     v2u out;
     out.x = w[0];
@@ -57,7 +51,7 @@ __global__ __launch_bounds__(kBlock) void k_quorum_active(u64 G, const u32* __re
     return;
   }
   const u64 g1 = g0 + kQaGpt < G ? g0 + kQaGpt : G;
-  for (u64 g = g0; g < g1; ++g) won[g] = quorum_active_one(cfg[g], active[g]);
+  for (u64 g = g0; g < g1; ++g) won[g] = quorum_active(cfg[g], active[g]);
 }
 
 // ---------------------------------------------------------- MsgAppResp -----

@@ -112,9 +112,7 @@ __device__ __forceinline__ u8 tally_at(Table tab, u32 g, u32 cfg, u32 votes0, u3
       if (!(rf[f] & QB_REC_REJECT)) gr |= 1u << s;
     }
   }
-  const u8 r1 = vote_from_counts(__popc(min_), __popc(min_ & gr), __popc(min_ & vd));
-  const u8 r2 = vote_from_counts(__popc(mout), __popc(mout & gr), __popc(mout & vd));
-  return joint_vote(r1, r2);
+  return masks_vote(min_, mout, gr, vd);
 }
 
 constexpr unsigned kRecBlocks = 2048;
@@ -269,11 +267,23 @@ __global__ __launch_bounds__(kBlock) void k_tally(u64 G, const u32* __restrict__
   const u32 voters = min_ | mout;
   if (granted_out) granted_out[g] = u8(__popc(voters & gr));
   if (rejected_out) rejected_out[g] = u8(__popc(voters & vd & ~gr));
-  if (result_out) {
-    const u8 r1 = vote_from_counts(__popc(min_), __popc(min_ & gr), __popc(min_ & vd));
-    const u8 r2 = vote_from_counts(__popc(mout), __popc(mout & gr), __popc(mout & vd));
-    result_out[g] = joint_vote(r1, r2);
-  }
+  if (result_out) result_out[g] = masks_vote(min_, mout, gr, vd);
+}
+
+// Workspace: the table's key and value columns (cap is a power of two >=
+// 1024, so both are whole 256-byte pieces) and one spare piece.
+struct Carve {
+  u64 cap;
+  size_t key, val, total;
+};
+inline Carve carve(u64 M) {
+  Carve c{};
+  Carver k;
+  c.cap = capacity_for(M);
+  c.key = k.take(c.cap * sizeof(u64));
+  c.val = k.take(c.cap * sizeof(u32));
+  c.total = k.o + 256;
+  return c;
 }
 
 }  // namespace vt
@@ -281,10 +291,7 @@ __global__ __launch_bounds__(kBlock) void k_tally(u64 G, const u32* __restrict__
 
 using namespace qb;
 
-extern "C" size_t qb_votes_workspace_bytes(uint64_t M) {
-  const u64 cap = vt::capacity_for(M);
-  return size_t(cap * sizeof(u64) + cap * sizeof(u32) + 256);
-}
+extern "C" size_t qb_votes_workspace_bytes(uint64_t M) { return vt::carve(M).total; }
 
 extern "C" int qb_dev_record_votes(int mode, uint64_t G, uint64_t M, const uint32_t* rec_group,
                                    const uint8_t* rec_flags, const uint64_t* rec_term,
@@ -303,13 +310,13 @@ extern "C" int qb_dev_record_votes(int mode, uint64_t G, uint64_t M, const uint3
   if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(stepdown_at/decided_at)");
   if (M == 0) return QB_OK;
   QB_REQUIRE(rec_group && rec_flags && rec_term, "record pointer is NULL");
-  const u64 cap = vt::capacity_for(M);
-  const size_t need = qb_votes_workspace_bytes(M);
+  const vt::Carve cv = vt::carve(M);
+  const u64 cap = cv.cap;
+  const size_t need = cv.total;
   QB_REQUIRE(workspace && workspace_bytes >= need,
              "workspace too small: need %zu bytes (qb_votes_workspace_bytes)", need);
   char* ws = static_cast<char*>(workspace);
-  vt::Table tab{reinterpret_cast<u64*>(ws), reinterpret_cast<u32*>(ws + cap * sizeof(u64)),
-                cap - 1};
+  vt::Table tab{reinterpret_cast<u64*>(ws + cv.key), reinterpret_cast<u32*>(ws + cv.val), cap - 1};
   e = hipMemsetAsync(tab.key, 0, cap * sizeof(u64), st);
   if (e == hipSuccess) e = hipMemsetAsync(tab.val, 0xFF, cap * sizeof(u32), st);
   if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(vote table)");

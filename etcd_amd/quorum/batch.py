@@ -26,6 +26,8 @@ import torch
 
 from .. import _lib
 from ._checks import FLAG, I16, I32, I64, U8, check_tensors
+from ._dev import grow_workspace, stats_dict
+from ._dev import stream_handle as _stream  # noqa: F401  (_stream(device[, stream]))
 
 INDEX_INF = (1 << 64) - 1
 
@@ -43,10 +45,6 @@ def from_u64(a, device) -> torch.Tensor:
 
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
-
-
-def _stream(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 def _check_outs(G: int, commit_out, vote_out) -> None:
@@ -384,7 +382,7 @@ class CsrGroups:
                        (decided_at, "decided_at", I32, self.G),
                        (stats, "stats", I64, len(_lib.QB_VSTAT_NAMES))))
         need = _lib.load().qb_votes_workspace_bytes(batch.M)
-        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        ws = grow_workspace(None, need, self.device)
         _lib.call("qb_dev_record_votes", _lib.QB_VOTE_MODE_PREVOTE if prevote else
                   _lib.QB_VOTE_MODE_VOTE, self.G, batch.M, _ptr(batch.group), _ptr(batch.flags),
                   _ptr(batch.term), _ptr(group_term), _ptr(self.cfg), _ptr(self.votes),
@@ -484,8 +482,7 @@ class FixedTracker:
         if rearm:
             self.stepdown_at.fill_(-1)
         need = _lib.load().qb_fixed_tracker_workspace_bytes(self.n, self.G, batch.M)
-        if getattr(self, "_ws", None) is None or self._ws.numel() < need:
-            self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        self._ws = grow_workspace(getattr(self, "_ws", None), need, self.device)
         _lib.call("qb_dev_fixed_tracker_step", self.n, self.G, batch.M, _ptr(batch.group),
                   _ptr(batch.flags), _ptr(batch.index), _ptr(batch.term), _ptr(self.term),
                   _ptr(self.term_start), _ptr(self.match), _ptr(self.next), _ptr(self.active),
@@ -496,7 +493,7 @@ class FixedTracker:
     def workspace(self, M: int) -> torch.Tensor:
         """A device workspace for one batch of M records (bucket / apply_bucketed)."""
         need = _lib.load().qb_fixed_tracker_workspace_bytes(self.n, self.G, M)
-        return torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        return grow_workspace(None, need, self.device)
 
     def bucket(self, batch: AppRespBatch, ws: torch.Tensor, stream=None):
         """First half of ``step`` (qb_dev_fixed_tracker_bucket): the batch sorted
@@ -506,7 +503,7 @@ class FixedTracker:
         check_tensors(((ws, "ws", U8, 1),))
         _lib.call("qb_dev_fixed_tracker_bucket", self.n, self.G, batch.M, _ptr(batch.group),
                   _ptr(batch.flags), _ptr(batch.index), _ptr(batch.term), _ptr(ws), ws.numel(),
-                  _stream(self.device) if stream is None else stream.cuda_stream)
+                  _stream(self.device, stream))
 
     def apply_bucketed(self, batch: AppRespBatch, ws: torch.Tensor,
                        advanced_out: Optional[torch.Tensor] = None, stream=None):
@@ -519,12 +516,11 @@ class FixedTracker:
                   _ptr(self.term_start), _ptr(self.match), _ptr(self.next), _ptr(self.active),
                   _ptr(self.committed), _ptr(self.stepdown_at), _ptr(advanced_out),
                   _ptr(self.stats), _ptr(ws), ws.numel(),
-                  _stream(self.device) if stream is None else stream.cuda_stream)
+                  _stream(self.device, stream))
         return advanced_out
 
     def stats_dict(self) -> dict:
-        v = self.stats.cpu().tolist()
-        return {k: v[i] for i, k in enumerate(_lib.QB_STAT_NAMES)}
+        return stats_dict(_lib.QB_STAT_NAMES, self.stats)
 
     def stepped_down(self) -> torch.Tensor:
         """Groups whose leader stepped down in the last batch (a higher-term
@@ -595,8 +591,7 @@ class CsrTracker:
         if rearm:
             self.stepdown_at.fill_(-1)
         need = _lib.load().qb_csr_tracker_workspace_bytes(self.G, self.max_slots, batch.M)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        self._ws = grow_workspace(self._ws, need, self.device)
         _lib.call("qb_dev_csr_tracker_step", self.G, self.max_slots, _ptr(self.off),
                   _ptr(self.cfg), batch.M, _ptr(batch.group), _ptr(batch.flags),
                   _ptr(batch.index), _ptr(batch.term), _ptr(self.term), _ptr(self.term_start),
@@ -606,8 +601,7 @@ class CsrTracker:
         return advanced_out
 
     def stats_dict(self) -> dict:
-        v = self.stats.cpu().tolist()
-        return {k: v[i] for i, k in enumerate(_lib.QB_STAT_NAMES)}
+        return stats_dict(_lib.QB_STAT_NAMES, self.stats)
 
     def stepped_down(self) -> torch.Tensor:
         """Groups whose leader stepped down in the last batch (a higher-term

@@ -15,6 +15,8 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ._dev import grow_workspace, stream_handle
+from ._dev import to_dev as _dev
 
 NONE, SIMPLE, ENTER_JOINT, ENTER_JOINT_AUTOLEAVE, LEAVE_JOINT = 0, 1, 2, 3, 4
 ADD_NODE, REMOVE_NODE, UPDATE_NODE, ADD_LEARNER = 0, 1, 2, 3
@@ -35,7 +37,6 @@ ERR_MESSAGES = {
 _P = C.c_void_p
 SLOT_ARRAYS = {"ids": np.uint64, "match": np.uint64, "next": np.uint64,
                "pending_snapshot": np.uint64, "pstate": np.uint8, "infl_pos": np.uint32}
-_SIGNED = {np.uint8: np.uint8, np.uint32: np.int32, np.uint64: np.int64}
 
 
 class _In(C.Structure):
@@ -54,13 +55,6 @@ class _Out(C.Structure):
 def error_text(code: int, err_id: int) -> str:
     msg = ERR_MESSAGES.get(code, f"error {code}")
     return msg.format(err_id) if "{}" in msg else msg
-
-
-def _dev(a, dt, device):
-    a = np.ascontiguousarray(np.asarray(a, dtype=dt))
-    if a.size == 0:
-        a = np.zeros(1, dt)
-    return torch.from_numpy(a.view(_SIGNED[dt]).copy()).to(device)
 
 
 # ``out`` of change_soa: element size per key; per-slot arrays share the slot
@@ -199,10 +193,9 @@ class ConfigTable:
         for k, v in o.items():
             setattr(out, k, v.data_ptr())
         need = _lib.load().qb_conf_change_workspace_bytes(G)
-        if getattr(self, "_ws", None) is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        self._ws = grow_workspace(getattr(self, "_ws", None), need, dev)
         _lib.call("qb_dev_conf_change", C.byref(i), C.byref(out), self._ws.data_ptr(), need,
-                  torch.cuda.current_stream(dev).cuda_stream)
+                  stream_handle(dev))
         self._last_out = (i, out, o)  # keep the argument blocks alive until the stream is synced
         S_new = int(o["new_off"][G].item())
         if S_new > cap:

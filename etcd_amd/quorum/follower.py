@@ -17,7 +17,8 @@ import torch
 
 from .. import _lib
 from ._checks import I32, I64, U8, check_tensors
-from .leader import _to_dev, _to_np
+from ._dev import stats_dict, stream_handle
+from ._dev import to_dev as _to_dev, to_np as _to_np
 from .tick import TickState
 
 FIN_HEARTBEAT, FIN_VOTE, FIN_PREVOTE, FIN_TIMEOUT_NOW, FIN_HOST = 0, 1, 2, 3, 4
@@ -140,8 +141,7 @@ class FollowerResult:
     inbox: Optional[FollowerInbox] = None
 
     def stats_dict(self) -> Dict[str, int]:
-        st = self.stats.cpu().tolist()
-        return {k: st[i] for i, k in enumerate(FSTAT_NAMES)}
+        return stats_dict(FSTAT_NAMES, self.stats)
 
     def responses(self) -> Iterator[dict]:
         """The messages to send, in batch order — after the HardState of every
@@ -199,10 +199,7 @@ def follower_step(groups: FollowerGroups, inbox: FollowerInbox, stream=None, *,
         (out.stop_at, "stop_at", I32, G), (out.gflags, "gflags", U8, G),
         (out.stats, "stats", I64, len(FSTAT_NAMES)),
         (out.workspace, "workspace", I64, (need + 7) // 8)))
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    elif hasattr(stream, "cuda_stream"):
-        stream = stream.cuda_stream
+    stream = stream_handle(dev, stream)
     fg = FollowerGroupsC(G=G, election_timeout=int(groups.election_timeout),
                          check_quorum=1 if groups.check_quorum else 0,
                          pre_vote=1 if groups.pre_vote else 0, reserved=0,

@@ -27,6 +27,8 @@ import torch
 
 from .. import _lib
 from ._checks import I32, I64, U8, check_tensors
+from ._dev import grow_workspace, stream_handle
+from ._dev import to_dev as _to_dev, to_np as _to_np
 
 MAX_RUNS = 8
 MAX_READQ = 16
@@ -83,21 +85,6 @@ GROUP_ARRAYS = {  # name -> numpy dtype (device storage uses the same bytes)
     "pending_snapshot": np.uint64, "pstate": np.uint8, "infl_pos": np.uint32,
     "infl_buf": np.uint64, "rq_ctx": np.uint64, "rq_index": np.uint64, "rq_meta": np.uint32,
 }
-_TORCH = {np.uint8: torch.uint8, np.uint32: torch.int32, np.uint64: torch.int64,
-          np.uint16: torch.int16}
-_SIGNED = {np.uint8: np.uint8, np.uint32: np.int32, np.uint64: np.int64, np.uint16: np.int16}
-
-
-def _to_dev(a: np.ndarray, dt, device) -> torch.Tensor:
-    a = np.ascontiguousarray(np.asarray(a, dtype=dt))
-    if a.size == 0:
-        a = np.zeros(1, dtype=dt)  # keep a valid device pointer
-    return torch.from_numpy(a.view(_SIGNED[dt]).copy()).to(device)
-
-
-def _to_np(t: torch.Tensor, dt, n: Optional[int] = None) -> np.ndarray:
-    a = t.detach().cpu().numpy().view(dt)
-    return a if n is None else a[:n]
 
 
 @dataclass
@@ -229,8 +216,7 @@ class LeaderGroups:
         M = inbox.M
         dev = self.device
         need = lib.qb_leader_workspace_bytes(self.G, M)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        self._ws = grow_workspace(self._ws, need, dev)
         if msg_cap is None:
             msg_cap = max(16, 8 * M + 4 * self.G)
         out = self._outputs(msg_cap)
@@ -243,7 +229,7 @@ class LeaderGroups:
         _lib.call("qb_dev_leader_step", C.byref(ls), C.byref(ib), out["msgs"].data_ptr(), msg_cap,
                   out["total"].data_ptr(), out["off"].data_ptr(), out["stepdown"].data_ptr(),
                   out["gflags"].data_ptr(), stats.data_ptr(), self._ws.data_ptr(),
-                  self._ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+                  self._ws.numel(), stream_handle(dev))
         if not fetch:
             return out, stats
         total = int(out["total"].cpu().item())
@@ -272,8 +258,7 @@ class LeaderGroups:
         lib = _lib.load()
         M, G, dev = inbox.M, self.G, self.device
         need = lib.qb_leader_outbox_workspace_bytes(G, M)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        self._ws = grow_workspace(self._ws, need, dev)
         if nchunks is None:
             nchunks = M // 8 + 1024
         ob = self._outbox(nchunks, read_states)
@@ -292,7 +277,7 @@ class LeaderGroups:
                            read_count=ob["read_count"].data_ptr() if read_states else None)
         _lib.call("qb_dev_leader_step_outbox", C.byref(ls), C.byref(ib), C.byref(oc),
                   ob["stepdown"].data_ptr(), ob["gflags"].data_ptr(), stats.data_ptr(),
-                  self._ws.data_ptr(), self._ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+                  self._ws.data_ptr(), self._ws.numel(), stream_handle(dev))
         if not fetch:
             return ob, stats
         return self.fetch_outbox(ob, stats, nchunks)

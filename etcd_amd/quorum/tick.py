@@ -18,7 +18,9 @@ import torch
 
 from .. import _lib
 from ._checks import I32, I64, U8, check_tensors
-from .leader import MAX_READQ, LeaderGroups, _to_dev, _to_np
+from ._dev import stats_dict, stream_handle
+from ._dev import to_dev as _to_dev, to_np as _to_np
+from .leader import MAX_READQ, LeaderGroups
 
 MSG_HEARTBEAT = 8
 ROLE_FOLLOWER, ROLE_CANDIDATE, ROLE_LEADER, ROLE_PRE_CANDIDATE = 0, 1, 2, 3
@@ -74,8 +76,7 @@ class TickResult:
     groups: LeaderGroups
 
     def stats_dict(self) -> Dict[str, int]:
-        st = self.stats.cpu().tolist()
-        return {k: st[i] for i, k in enumerate(TSTAT_NAMES)}
+        return stats_dict(TSTAT_NAMES, self.stats)
 
     def heartbeats(self, g: int) -> List[dict]:
         """Group g's MsgHeartbeats of this tick, in the order the reference
@@ -126,10 +127,7 @@ def leader_tick(groups: LeaderGroups, state: TickState, election_timeout: int,
                    (state.rand_timeout, "state.rand_timeout", I32, G),
                    (out.tflags, "tflags", U8, G), (out.hb_commit, "hb_commit", I64, S),
                    (out.hb_ctx, "hb_ctx", I64, G), (out.stats, "stats", I64, len(TSTAT_NAMES))))
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    elif hasattr(stream, "cuda_stream"):
-        stream = stream.cuda_stream
+    stream = stream_handle(dev, stream)
     tg = TickGroupsC(G=G, readq_cap=groups.readq_cap, election_timeout=int(election_timeout),
                      heartbeat_timeout=int(heartbeat_timeout), check_quorum=1 if check_quorum else 0,
                      off=t["off"].data_ptr(), cfg=t["cfg"].data_ptr(), meta=t["meta"].data_ptr(),

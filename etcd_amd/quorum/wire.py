@@ -9,6 +9,7 @@ import torch
 
 from .. import _lib
 from ._checks import check_tensors as _check_tensors
+from ._dev import grow_workspace, stream_handle
 from .leader import LeaderInbox
 
 WIRE_OK, WIRE_UNMARSHAL, WIRE_TYPE, WIRE_CTX = 0, 1, 2, 3
@@ -33,7 +34,7 @@ def group_rows(off: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
     G = off.numel() - 1
     rows = torch.empty(max(G, 1) * 8, dtype=torch.int64, device=off.device)
     _lib.call("qb_dev_wire_group_rows", G, off.data_ptr(), ids.data_ptr(), rows.data_ptr(),
-              torch.cuda.current_stream(off.device).cuda_stream)
+              stream_handle(off.device))
     return rows
 
 
@@ -75,14 +76,14 @@ def ingest(buf: torch.Tensor, nbytes: int, msg_off: torch.Tensor, msg_group: tor
                   rf.data_ptr(), ri.data_ptr(), rt.data_ptr(), rh.data_ptr(), rl.data_ptr(),
                   status.data_ptr(), mtype.data_ptr(),
                   None if stats is None else stats.data_ptr(),
-                  torch.cuda.current_stream(dev).cuda_stream)
+                  stream_handle(dev))
     else:
         _lib.call("qb_dev_ingest_messages_rows", M, buf.data_ptr(), nbytes, msg_off.data_ptr(),
                   msg_group.data_ptr(), G, rows.data_ptr(), ids.data_ptr(), rg.data_ptr(),
                   rf.data_ptr(), ri.data_ptr(), rt.data_ptr(), rh.data_ptr(), rl.data_ptr(),
                   status.data_ptr(), mtype.data_ptr(),
                   None if stats is None else stats.data_ptr(),
-                  torch.cuda.current_stream(dev).cuda_stream)
+                  stream_handle(dev))
     ib = LeaderInbox(rg, rf, ri, rt, rh, rl)
     ib._m = M
     return ib, status[:M], mtype[:M]
@@ -128,12 +129,10 @@ def ingest_tracker_step(tracker, buf: torch.Tensor, nbytes: int, msg_off: torch.
             else lib.qb_wire_fixed_tracker_workspace_bytes(tracker.n, tracker.G, M))
     if need == 0:
         raise _lib.QuorumBatchError(f"batch of {M} messages too large for one call")
-    ws = getattr(tracker, "_wire_ws", None)
-    if ws is None or ws.numel() < need:
-        ws = tracker._wire_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = tracker._wire_ws = grow_workspace(getattr(tracker, "_wire_ws", None), need, dev)
     status = torch.empty(max(M, 1), dtype=torch.uint8, device=dev)
     p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    stream = torch.cuda.current_stream(dev).cuda_stream
+    stream = stream_handle(dev)
     state = (p(tracker.term), p(tracker.term_start), p(tracker.match), p(tracker.next),
              p(tracker.active), p(tracker.committed), p(tracker.stepdown_at), p(advanced_out),
              status.data_ptr(), p(wire_stats), p(tracker.stats), ws.data_ptr(), ws.numel(), stream)

@@ -163,6 +163,7 @@ def route_partition(cols: Dict[str, torch.Tensor], total: int, world: int):
     stably partitioned by owner rank, group rebased to the owner's local
     index.  Returns (send columns, per-rank counts)."""
     from etcd_amd import _lib
+    from etcd_amd.quorum._dev import stream_handle
     lib = _lib.load()
     unknown = set(cols) - set(_ROUTE_COLS)
     if unknown:
@@ -178,7 +179,7 @@ def route_partition(cols: Dict[str, torch.Tensor], total: int, world: int):
     def ptr(d, name):
         t = d.get(name)
         return t.data_ptr() if t is not None else None
-    stream = torch.cuda.current_stream(dev).cuda_stream
+    stream = stream_handle(dev)
     _lib.check(lib.qb_dev_route_partition(
         total, world, M, *[ptr(cols, n) for n in _ROUTE_COLS], *[ptr(send, n) for n in _ROUTE_COLS],
         off.data_ptr(), ws.data_ptr(), nbytes, stream), "qb_dev_route_partition")
@@ -208,6 +209,7 @@ def compact_changed(changed: torch.Tensor, commit: torch.Tensor, g_base: int = 0
         idx = torch.nonzero(changed, as_tuple=True)[0]
         return (idx + g_base).to(torch.int32), commit[idx]
     from etcd_amd import _lib
+    from etcd_amd.quorum._dev import stream_handle
     lib = _lib.load()
     n = commit.numel()
     dev = commit.device
@@ -218,8 +220,7 @@ def compact_changed(changed: torch.Tensor, commit: torch.Tensor, g_base: int = 0
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
     _lib.check(lib.qb_dev_compact_changed(n, changed.data_ptr(), commit.data_ptr(), g_base,
                                           gid.data_ptr(), val.data_ptr(), cnt.data_ptr(),
-                                          ws.data_ptr(), nbytes,
-                                          torch.cuda.current_stream(dev).cuda_stream),
+                                          ws.data_ptr(), nbytes, stream_handle(dev)),
                "qb_dev_compact_changed")
     k = int(cnt.item())
     return gid[:k], val[:k]

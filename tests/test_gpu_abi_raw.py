@@ -61,6 +61,9 @@ def test_malloc_reports_enomem():
     assert lib.qb_last_error()
 
 
+GUARD = 4096
+
+
 class Stream:
     """qb_stream_create / sync / destroy plus a Dev allocator, as the cgo
     package holds them."""
@@ -71,6 +74,7 @@ class Stream:
         self.st = C.c_void_p()
         _lib.check(self.lib.qb_stream_create(C.byref(self.st)), "qb_stream_create")
         self.d = Dev()
+        self.guards = []
 
     def up(self, a):
         a = np.ascontiguousarray(a)
@@ -84,6 +88,28 @@ class Stream:
         p = self.d.alloc(max(nbytes, 16))
         _lib.check(self.lib.qb_memset_async(p, value, max(nbytes, 16), self.st), "memset")
         return p
+
+    def guarded(self, nbytes):
+        """A zeroed workspace of exactly ``nbytes`` with a GUARD-byte margin of
+        0xA5 on either side, all inside one allocation: a write outside the
+        declared workspace lands in a margin and ``check_guards`` fails (it
+        cannot fault)."""
+        base = self.d.alloc(nbytes + 2 * GUARD)
+        for at, n, value in ((base, GUARD, 0xA5), (base + GUARD, nbytes, 0),
+                             (base + GUARD + nbytes, GUARD, 0xA5)):
+            if n:
+                _lib.check(self.lib.qb_memset_async(at, value, n, self.st), "memset")
+        self.guards.append((base, nbytes))
+        return base + GUARD
+
+    def check_guards(self):
+        """Both margins of every ``guarded`` workspace still hold 0xA5."""
+        for base, nbytes in self.guards:
+            for name, at in (("before", base), ("after", base + GUARD + nbytes)):
+                m = self.down(at, np.empty(GUARD, np.uint8))
+                bad = np.flatnonzero(m != 0xA5)
+                assert bad.size == 0, (f"{bad.size} byte(s) written {name} a workspace of "
+                                       f"{nbytes} bytes, first at margin offset {bad[0]}")
 
     def down(self, p, like):
         out = np.empty_like(like)
@@ -221,13 +247,11 @@ def test_csr_tracker_raw_abi():
     s.close()
 
 
-def test_votes_raw_abi():
-    """qb_dev_record_votes + qb_dev_csr_tally_votes through the raw ABI against
-    the sequential candidate oracle (tests/test_gpu_votes.py restatement)."""
+def _votes_raw(M):
     from tests.test_gpu_votes import sequential_votes
     s = Stream()
     lib = s.lib
-    G, M = 3000, 9000
+    G = 3000
     rng = np.random.default_rng(5)
     cc = batch.compile_configs([set(rng.choice(20, size=int(rng.integers(1, 8)), replace=False)
                                     + 1) for _ in range(G)])
@@ -246,7 +270,7 @@ def test_votes_raw_abi():
     d_votes, d_sd, d_dec, d_stats = s.zeros(4 * G), s.zeros(4 * G), s.zeros(4 * G), s.zeros(64)
     d_g, d_f, d_t = s.up(group), s.up(flags), s.up(term)
     need = lib.qb_votes_workspace_bytes(M)
-    ws = s.zeros(need)
+    ws = s.guarded(need)
     _lib.check(lib.qb_dev_record_votes(0, G, M, d_g, d_f, d_t, d_gt, d_cfg, d_votes, d_sd, d_dec,
                                        d_stats, ws, need, s.st), "record votes")
     res = s.zeros(G)
@@ -255,7 +279,23 @@ def test_votes_raw_abi():
     assert np.array_equal(s.down(d_sd, np.empty(G, np.uint32)), want_sd)
     assert np.array_equal(s.down(d_dec, np.empty(G, np.uint32)), want_dec)
     assert np.array_equal(s.down(d_stats, np.empty(8, np.uint64)), want_stats)
+    s.check_guards()
     s.close()
+
+
+def test_votes_raw_abi():
+    """qb_dev_record_votes + qb_dev_csr_tally_votes through the raw ABI against
+    the sequential candidate oracle (tests/test_gpu_votes.py restatement); the
+    workspace holds exactly qb_votes_workspace_bytes(M) and nothing is written
+    outside it."""
+    _votes_raw(9000)
+
+
+@pytest.mark.parametrize("M", [1, 513])
+def test_votes_raw_abi_small_tables(M):
+    """The same with the smallest vote table (M = 1) and the first doubled one
+    (M = 513)."""
+    _votes_raw(M)
 
 
 def test_comm_allgather_world1_raw_abi():
@@ -274,10 +314,11 @@ def test_comm_allgather_world1_raw_abi():
     d_c, d_v = s.up(c), s.up(v)
     o_c, o_v = s.zeros(8 * G), s.zeros(G)
     need = lib.qb_allgather_workspace_bytes(G, 1)
-    ws = s.zeros(need)
+    ws = s.guarded(need)
     _lib.check(lib.qb_dev_allgather_results(comm, G, d_c, d_v, o_c, o_v, ws, need, s.st),
                "allgather")
     assert np.array_equal(s.down(o_c, c), c) and np.array_equal(s.down(o_v, v), v)
+    s.check_guards()
     _lib.check(lib.qb_comm_destroy(comm), "comm destroy")
     s.close()
 
@@ -296,7 +337,7 @@ def test_compact_and_scatter_changed_raw_abi(n, frac, base):
     d_ch, d_c = s.up(changed), s.up(commit)
     gid, val, cnt = s.zeros(4 * n + 8), s.zeros(8 * n + 8), s.zeros(8)
     need = lib.qb_compact_changed_workspace_bytes(n)
-    ws = s.zeros(need)
+    ws = s.guarded(need)
     _lib.check(lib.qb_dev_compact_changed(n, d_ch, d_c, base, gid, val, cnt, ws, need, s.st),
                "compact")
     idx = np.nonzero(changed)[0]
@@ -312,6 +353,7 @@ def test_compact_and_scatter_changed_raw_abi(n, frac, base):
     want = np.zeros(total, np.uint64)
     want[idx + base] = commit[idx]
     assert np.array_equal(s.down(out, np.empty(total, np.uint64)), want)
+    s.check_guards()
     s.close()
 
 
@@ -327,7 +369,7 @@ def test_allgather_changed_world1_raw_abi():
     _lib.check(lib.qb_comm_init(C.byref(comm), 1, 0, uid), "comm init")
     G = 300007
     need = lib.qb_allgather_changed_workspace_bytes(G, 1)
-    ws = s.zeros(need)
+    ws = s.guarded(need)
     d_all = s.up(np.zeros(G, np.uint64))
     want = np.zeros(G, np.uint64)
     rng = np.random.default_rng(5)
@@ -341,6 +383,7 @@ def test_allgather_changed_world1_raw_abi():
         want = np.where(changed != 0, commit, want)
         assert n.value == int(changed.sum())
         assert np.array_equal(s.down(d_all, np.empty(G, np.uint64)), want)
+        s.check_guards()
     _lib.check(lib.qb_comm_destroy(comm), "comm destroy")
     s.close()
 
@@ -361,7 +404,8 @@ def _route_ref(total, world, grp, cols):
 
 @pytest.mark.parametrize("world,total,M,opt", [(1, 1000, 5000, True), (2, 100003, 300001, False),
                                                (3, 7, 20000, True), (8, 1 << 20, 1 << 20, True),
-                                               (64, 100000, 70001, False), (5, 0, 1000, True)])
+                                               (64, 100000, 70001, False), (5, 0, 1000, True),
+                                               (3, 10, 1, True), (3, 1000, 1025, False)])
 def test_route_partition_raw_abi(world, total, M, opt):
     """qb_dev_route_partition against the stable host partition: owners from
     qb_shard_range, groups >= total to the last rank, the columns moved in
@@ -382,7 +426,7 @@ def test_route_partition_raw_abi(world, total, M, opt):
     dout = {k: s.zeros(v.nbytes) for k, v in cols.items()}
     off = s.zeros(4 * (world + 1))
     need = lib.qb_route_partition_workspace_bytes(world, M)
-    ws = s.zeros(need)
+    ws = s.guarded(need)
     _lib.check(lib.qb_dev_route_partition(total, world, M, *[din.get(n) for n in names],
                                           *[dout.get(n) for n in names], off, ws, need, s.st),
                "route partition")
@@ -391,6 +435,7 @@ def test_route_partition_raw_abi(world, total, M, opt):
         assert np.array_equal(s.down(dout[k], v), ref[k]), k
     o = s.down(off, np.empty(world + 1, np.uint32))
     assert np.array_equal(np.diff(o.astype(np.int64)), counts) and o[0] == 0 and o[-1] == M
+    s.check_guards()
     s.close()
 
 
@@ -414,7 +459,7 @@ def test_route_records_world1_raw_abi():
     din = {k: s.up(v) for k, v in cols.items()}
     dout = {k: s.zeros(v.nbytes) for k, v in cols.items()}
     need = lib.qb_route_workspace_bytes(1, M)
-    ws = s.zeros(need)
+    ws = s.guarded(need)
     cnt = C.c_uint64(0)
     rc = lib.qb_dev_route_records(comm, total, M, *[din[n] for n in names], None, None,
                                   *[dout[n] for n in names], None, None, M - 1, C.byref(cnt),
@@ -426,6 +471,7 @@ def test_route_records_world1_raw_abi():
     assert cnt.value == M
     for k, v in cols.items():
         assert np.array_equal(s.down(dout[k], v), v), k
+    s.check_guards()
     _lib.check(lib.qb_comm_destroy(comm), "comm destroy")
     s.close()
 

@@ -89,12 +89,28 @@ def _err():
     return fake().qb_last_error().decode()
 
 
+GUARD = 4096
+
+
+def guarded(nbytes, device=DEV):
+    """(buffer, workspace): a workspace of exactly ``nbytes`` between two
+    GUARD-byte margins of 0xA5 in one allocation, so a write outside the
+    declared workspace shows in ``margins_intact`` instead of landing in a
+    neighbouring allocation (it cannot fault)."""
+    buf = torch.full((nbytes + 2 * GUARD,), 0xA5, dtype=torch.uint8, device=device)
+    return buf, buf[GUARD:GUARD + nbytes]
+
+
+def margins_intact(buf) -> bool:
+    return bool((buf[:GUARD] == 0xA5).all().item() and (buf[-GUARD:] == 0xA5).all().item())
+
+
 def u64(a):
     return torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64)).to(DEV)
 
 
 @pytest.mark.parametrize("world,total", [(2, 1 << 20), (3, 1000003), (8, 8 * 4099 + 5),
-                                         (8, 7), (3, 0)])
+                                         (8, 7), (3, 0), (3, 10)])
 def test_allgather_results_world_n(world, total):
     """qb_dev_allgather_results: every rank ends with the node-wide commit /
     vote vectors, shards in rank order — even shards gathered in place,
@@ -109,12 +125,12 @@ def test_allgather_results_world_n(world, total):
     ws_bytes = lib.qb_allgather_workspace_bytes(total, world)
     outs = [(torch.full((max(total, 1),), -1, dtype=torch.int64, device=DEV),
              torch.full((max(total, 1),), 0xEE, dtype=torch.uint8, device=DEV),
-             torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=DEV)) for _ in range(world)]
+             guarded(ws_bytes)) for _ in range(world)]
     torch.cuda.synchronize()
 
     def body(r, comm, st):
         b, e = shard_range(total, world, r)
-        ca, va, ws = outs[r]
+        ca, va, (_, ws) = outs[r]
         rc = lib.qb_dev_allgather_results(comm, total, d_commit[b:].data_ptr() if e > b else None,
                                           d_vote[b:].data_ptr() if e > b else None,
                                           ca.data_ptr(), va.data_ptr(), ws.data_ptr(), ws.numel(),
@@ -123,9 +139,10 @@ def test_allgather_results_world_n(world, total):
     run_ranks(world, body)
     torch.cuda.synchronize()
     for r in range(world):
-        ca, va, _ = outs[r]
+        ca, va, (buf, _) = outs[r]
         assert np.array_equal(ca[:total].cpu().numpy().view(np.uint64), commit), r
         assert np.array_equal(va[:total].cpu().numpy(), vote), r
+        assert margins_intact(buf), r
 
 
 def _delta_ticks(rng, total, world):
@@ -138,7 +155,7 @@ def _delta_ticks(rng, total, world):
             np.ones(total, bool), skew]
 
 
-@pytest.mark.parametrize("world,total", [(2, 200000), (3, 100003), (8, 8 * 5001 + 3)])
+@pytest.mark.parametrize("world,total", [(2, 200000), (3, 100003), (8, 8 * 5001 + 3), (3, 10)])
 def test_allgather_changed_world_n(world, total):
     """qb_dev_allgather_changed over five ticks: the node-wide commit vector
     every rank keeps equals the start vector with every changed group's new
@@ -150,7 +167,7 @@ def test_allgather_changed_world_n(world, total):
     want = rng.integers(0, 1 << 62, size=total, dtype=np.uint64)
     ws_bytes = lib.qb_allgather_changed_workspace_bytes(total, world)
     alls = [u64(want) for _ in range(world)]
-    wss = [torch.empty(ws_bytes, dtype=torch.uint8, device=DEV) for _ in range(world)]
+    bufs, wss = zip(*[guarded(ws_bytes) for _ in range(world)])
     for tick, changed in enumerate(_delta_ticks(rng, total, world)):
         commit = want.copy()
         commit[changed] = rng.integers(0, 1 << 63, size=int(changed.sum()), dtype=np.uint64)
@@ -172,6 +189,7 @@ def test_allgather_changed_world_n(world, total):
         want = commit
         for r in range(world):
             assert np.array_equal(alls[r].cpu().numpy().view(np.uint64), want), (tick, r)
+            assert margins_intact(bufs[r]), (tick, r)
 
 
 def test_allgather_changed_local_failure_reaches_every_rank():
@@ -184,7 +202,7 @@ def test_allgather_changed_local_failure_reaches_every_rank():
     d_commit = torch.arange(total, dtype=torch.int64, device=DEV)
     ca = [torch.zeros(total, dtype=torch.int64, device=DEV) for _ in range(world)]
     ws_bytes = lib.qb_allgather_changed_workspace_bytes(total, world)
-    wss = [torch.empty(ws_bytes, dtype=torch.uint8, device=DEV) for _ in range(world)]
+    bufs, wss = zip(*[guarded(ws_bytes) for _ in range(world)])
     torch.cuda.synchronize()
 
     def body(r, comm, st):
@@ -199,6 +217,8 @@ def test_allgather_changed_local_failure_reaches_every_rank():
     assert all(rc == QB_EINVAL for rc, _ in res), res
     assert "NULL" in res[1][1]                              # the failing rank's own reason
     assert all("rank 1 failed" in msg for r, (_, msg) in enumerate(res) if r != 1), res
+    torch.cuda.synchronize()
+    assert all(margins_intact(b) for b in bufs)
 
 
 def _route_expected(batches, total, world):
@@ -250,8 +270,8 @@ def test_route_records_world_n(world, total, with_hint):
     cap = sum(sizes)
     outs = [{k: torch.zeros(cap, dtype=torch.int64, device=DEV) for k in names}
             for _ in range(world)]
-    wss = [torch.empty(lib.qb_route_workspace_bytes(world, sizes[r]) or 1, dtype=torch.uint8,
-                       device=DEV) for r in range(world)]
+    bufs, wss = zip(*[guarded(lib.qb_route_workspace_bytes(world, sizes[r]))
+                      for r in range(world)])
     torch.cuda.synchronize()
 
     def body(r, comm, st):
@@ -275,6 +295,7 @@ def test_route_records_world_n(world, total, with_hint):
             w = exp[d][k].dtype.itemsize
             got = raw[: n * w].view(exp[d][k].dtype)
             assert np.array_equal(got, exp[d][k]), (d, k)
+        assert margins_intact(bufs[d]), d
 
 
 @pytest.mark.parametrize("fail", ["capacity", "null_output"])
@@ -291,8 +312,7 @@ def test_route_records_local_failure_reaches_every_rank(fail):
              "term": torch.ones(M, dtype=torch.int64, device=DEV)} for _ in range(world)]
     outs = [{k: torch.zeros(world * M, dtype=torch.int64, device=DEV)
              for k in ("group", "flags", "index", "term")} for _ in range(world)]
-    wss = [torch.empty(lib.qb_route_workspace_bytes(world, M), dtype=torch.uint8, device=DEV)
-           for _ in range(world)]
+    bufs, wss = zip(*[guarded(lib.qb_route_workspace_bytes(world, M)) for _ in range(world)])
     torch.cuda.synchronize()
 
     def body(r, comm, st):
@@ -312,3 +332,5 @@ def test_route_records_local_failure_reaches_every_rank(fail):
     res = run_ranks(world, body)
     assert all(rc == QB_EINVAL for rc, _ in res), res
     assert all("rank 2 would receive" in msg for _, msg in res), res
+    torch.cuda.synchronize()
+    assert all(margins_intact(b) for b in bufs)

@@ -105,6 +105,40 @@ def test_random_sequences(seed):
                                                           "pstate", "infl_pos", "infl_buf")}, 7)
 
 
+@pytest.mark.parametrize("G", [1, 4097])
+def test_change_stays_inside_its_workspace(G):
+    """One random change over G groups (1: the smallest workspace; 4097: two
+    scan blocks) with the table's cached workspace seeded by a view of exactly
+    qb_conf_change_workspace_bytes(G) bytes between two 0xA5 margins: the
+    result equals the oracle's and neither margin is written."""
+    from etcd_amd import _lib
+    from etcd_amd.quorum.confchange import error_text
+    from tests.test_gpu_comm_fake import guarded, margins_intact
+    r = random.Random(G)
+    orc = [CC.Tracker.empty(7) for _ in range(G)]
+    table = _table(orc, K=7)
+    for step in range(2):  # the second change acts on populated configs
+        op = [CP.random_op(r, t) for t in orc]
+        ccs = [CP.random_ccs(r) for _ in orc]
+        last = [r.randint(0, 1000) for _ in orc]
+        need = _lib.fn("qb_conf_change_workspace_bytes")(G)
+        buf, table._ws = guarded(need, table.t["off"].device)
+        new, err, err_id = table.change(op, ccs, last)
+        assert table._ws.data_ptr() == buf.data_ptr() + 4096  # the seeded view was used
+        assert margins_intact(buf), step
+        dev = CP.unpack(new.numpy(), 7)
+        for g in range(G):
+            nt, e = CP.oracle_apply(orc[g], op[g], ccs[g], last[g])
+            if e is None and sum(1 for _ in nt.prs) > 16:
+                e = "more than 16 members, or 24 alive within one change (engine limit)"
+                nt = orc[g]
+            got_e = error_text(int(err[g]), int(err_id[g])) if err[g] else None
+            assert got_e == e, (step, g, op[g], ccs[g], got_e, e)
+            assert _render(dev[g]) == _render(nt), (step, g)
+            orc[g] = nt
+        table = new
+
+
 def test_churn_within_one_change_list():
     """a Simple change that adds and removes more than 8 learners in
     one list (the final config keeps its 5 voters) is legal in the reference;
