@@ -340,6 +340,12 @@ class LeaderGroups:
         return leader_tick(self, state, election_timeout, heartbeat_timeout, check_quorum,
                            stream, out=out)
 
+    def campaign(self, election, action, stream=None, out=None):
+        """MsgHup / election outcomes over these groups
+        (etcd_amd.quorum.campaign.campaign)."""
+        from .campaign import campaign
+        return campaign(self, election, action, stream, out=out)
+
     def _outbox(self, nchunks: int, read_states: bool = False):
         dev, G = self.device, self.G
         key = ("outbox", nchunks, read_states)

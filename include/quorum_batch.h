@@ -411,7 +411,8 @@ int qb_dev_csr_tracker_step(uint64_t G, uint32_t max_slots, const uint32_t* off,
  *                  group term.  Nothing after the step-down is applied.
  * Both outputs are written for every group (no entry requirement).  The
  * state change itself (campaign with ResetVotes, becomeLeader, becomeFollower)
- * is the host's.  workspace: qb_votes_workspace_bytes(M) bytes of device
+ * is qb_dev_campaign's (QB_CAMP_WON / QB_CAMP_LOST), the step-down at a higher
+ * term the host's.  workspace: qb_votes_workspace_bytes(M) bytes of device
  * scratch. */
 size_t qb_votes_workspace_bytes(uint64_t M);
 int qb_dev_record_votes(int mode, uint64_t G, uint64_t M,
@@ -686,7 +687,7 @@ int qb_dev_leader_step_outbox(const qb_leader_groups* lg, const qb_leader_inbox*
 #define QB_ROLE_PROMOTABLE 0x80u /* raft.promotable(), maintained by the host */
 
 /* Per-group output flags of the tick. */
-#define QB_TFLAG_HUP 0x01u              /* election timeout: the host campaigns */
+#define QB_TFLAG_HUP 0x01u              /* election timeout: campaign (QB_CAMP_HUP) */
 #define QB_TFLAG_BEAT 0x02u             /* heartbeats written                   */
 #define QB_TFLAG_STEPPED_DOWN 0x04u     /* CheckQuorum failed (= QB_LFLAG_STEPPED_DOWN) */
 #define QB_TFLAG_CHECK_QUORUM 0x08u     /* the MsgCheckQuorum step ran          */
@@ -811,7 +812,7 @@ int qb_dev_leader_tick(const qb_tick_groups* tg, uint8_t* tflags, uint64_t* hb_c
 #define QB_FRESP_REJECT 0x80u
 
 #define QB_FFLAG_HOST_MSG 0x01u     /* stopped at a QB_FIN_HOST record        */
-#define QB_FFLAG_CAMPAIGN 0x02u     /* stopped at MsgTimeoutNow: hup(transfer) */
+#define QB_FFLAG_CAMPAIGN 0x02u     /* stopped at MsgTimeoutNow: QB_CAMP_TRANSFER */
 #define QB_FFLAG_COMMIT_RANGE 0x04u /* stopped at a Commit past last_index    */
 #define QB_FFLAG_RESET 0x08u        /* becomeFollower ran: the host's reset   */
 #define QB_FFLAG_HARDSTATE 0x10u    /* term / vote / committed changed        */
@@ -871,6 +872,152 @@ int qb_dev_follower_step(const qb_follower_groups* fg, const qb_follower_inbox* 
                          uint8_t* resp_type, uint64_t* resp_term, uint32_t* stop_at,
                          uint8_t* gflags, uint64_t* stats, void* workspace,
                          size_t workspace_bytes, void* stream);
+
+/* ----------------------------------------------------------------------- */
+/* Campaign: MsgHup and election outcomes                                  */
+/* ----------------------------------------------------------------------- */
+
+/* The state changes of an election for G groups in one call: Step(MsgHup) ->
+ * hup -> campaign -> becomePreCandidate / becomeCandidate -> poll self ->
+ * vote requests (raft.go:760-845), and becomeLeader (+ bcastAppend) or
+ * becomeFollower once qb_dev_csr_tally_votes has the result (stepCandidate,
+ * raft.go:1399-1414).  It is the piece between qb_dev_leader_tick's
+ * QB_TFLAG_HUP / qb_dev_follower_step's QB_FFLAG_CAMPAIGN and the vote
+ * requests that qb_dev_follower_step answers, and between the tally and the
+ * new leader's first tick.  action[g], one byte per group, groups independent:
+ *   QB_CAMP_NONE      nothing;
+ *   QB_CAMP_HUP       Step(MsgHup): hup(campaignPreElection) with pre_vote,
+ *                     else hup(campaignElection) (raft.go:922-928);
+ *   QB_CAMP_TRANSFER  hup(campaignTransfer) (raft.go:1452-1457);
+ *   QB_CAMP_WON       VoteWon: a pre-candidate runs campaign(campaignElection),
+ *                     a candidate becomeLeader + bcastAppend;
+ *   QB_CAMP_LOST      VoteLost: becomeFollower(term, None);
+ *   | QB_CAMP_PENDING_CONF on HUP / TRANSFER: the host's answer to
+ *                     numOfPendingConf(unapplied) != 0 && committed > applied
+ *                     (raft.go:770-777; the log is the host's).
+ * The code is action & 0x7F; QB_CAMP_PENDING_CONF on any other code means
+ * nothing, and a code above QB_CAMP_LOST is treated as QB_CAMP_NONE and
+ * counted (QB_CSTAT_BAD_ACTION).  WON / LOST on a group that is neither
+ * candidate nor pre-candidate is ignored (QB_CFLAG_IGNORED).
+ *
+ * hup (raft.go:760-781) is ignored, in this order, by a leader, by a node that
+ * is not promotable (promotable: QB_ROLE_PROMOTABLE is set, the own slot —
+ * meta bits 0-7, "the leader slot" of the other calls, in every role — is
+ * below the group's slot count and is a voter of either half) and under
+ * QB_CAMP_PENDING_CONF; a (pre-)candidate whose timer fired again campaigns
+ * again.
+ * becomePreCandidate (raft.go:708-722): votes := 0, lead := 0, role :=
+ *   PreCandidate with the other bits of the byte kept; nothing else changes.
+ * becomeCandidate (raft.go:695-706): reset(term + 1), vote := self_id, role :=
+ *   Candidate.
+ * reset(t) (raft.go:590-619): term := t and vote := 0 if the term differs;
+ *   lead := 0, both counters 0, meta transferee := 0xFF, meta pending-read
+ *   count (bits 20-24) := 0, votes := 0, and for every slot of the group
+ *   match := 0 (own slot: last_index), next := last_index + 1, pstate :=
+ *   QB_PR_PROBE with no flag bits, pending_snapshot := 0, infl_pos := 0 (the
+ *   ring's contents are dead).  No slot is read.
+ * poll self (raft.go:803, 837-845) after either become: votes := bit | bit <<
+ *   16 for the own slot (no bit for an own slot >= 16), then
+ *   JointConfig.VoteResult against cfg.  VoteWon from a pre-campaign continues
+ *   with becomeCandidate and polls again; VoteWon from a candidacy continues
+ *   with becomeLeader, without bcastAppend (raft.go:803-811).  Otherwise the
+ *   vote requests are per-group outputs (raft.go:813-834):
+ *     req_type[g] = 5 (pb.MsgVote) or 17 (pb.MsgPreVote), | QB_CREQ_TRANSFER
+ *                   when the Context is "CampaignTransfer";
+ *     req_term[g] = term after the become, term + 1 for a pre-vote;
+ *     req_mask[g] = the voters of either half minus the own slot: one message
+ *                   per set bit, ascending (ascending IDs are ascending slots),
+ *                   Index / LogTerm = last_index[g] / last_term[g].
+ * becomeLeader (raft.go:724-758): reset(term), lead := self_id, role := Leader;
+ *   the own slot, if there is one: pstate := QB_PR_REPLICATE, then
+ *   appendEntry's MaybeUpdate(last_index + 1): match := last_index + 1, next :=
+ *   last_index + 2 (through Go's comparisons, so a wrapped index moves
+ *   neither back); maybeCommit: committed := last_index + 1 iff that exceeds
+ *   it, the config has a voter and every non-empty half is {own slot}.  The
+ *   empty entry itself, last_index / last_term, the term-run table and
+ *   pendingConfIndex are the log's and stay the host's
+ *   (QB_CFLAG_BECAME_LEADER); the call uses last_index as it stood at entry.
+ * QB_CAMP_WON as a candidate also runs bcastAppend (raft.go:515-522, 432-492)
+ *   on the Progress: every slot but the own becomes QB_PR_PROBE |
+ *   QB_PR_PROBE_SENT, QB_CFLAG_BCAST_APPEND, and the host forms per such
+ *   slot, ascending, MsgApp{Index: last_index, LogTerm: last_term, Commit:
+ *   committed[g], one entry}.
+ * becomeFollower(term, None) (raft.go:686-693): reset(term), role := Follower.
+ * term + 1 and last_index + 1 wrap as Go's uint64 does.  A slot count above
+ * QB_MAX_SLOTS is read as QB_MAX_SLOTS.
+ *
+ * The host's share of QB_CFLAG_RESET: the new randomized timeout,
+ * uncommittedSize and the readOnly contents. */
+#define QB_CAMP_NONE 0
+#define QB_CAMP_HUP 1
+#define QB_CAMP_TRANSFER 2
+#define QB_CAMP_WON 3
+#define QB_CAMP_LOST 4
+#define QB_CAMP_PENDING_CONF 0x80u
+
+#define QB_MSG_VOTE 5      /* pb.MsgVote    (raft.pb.go:76-94) */
+#define QB_MSG_PREVOTE 17  /* pb.MsgPreVote                    */
+#define QB_CREQ_TRANSFER 0x80u /* Context: "CampaignTransfer" (raft.go:829-832) */
+
+#define QB_CFLAG_REQUESTS 0x01u      /* req_type / req_term / req_mask hold requests */
+#define QB_CFLAG_BECAME_LEADER 0x02u /* the host appends the empty entry              */
+#define QB_CFLAG_BCAST_APPEND 0x04u  /* the host sends the first MsgApp to every peer */
+#define QB_CFLAG_RESET 0x08u         /* reset ran (= QB_FFLAG_RESET)                  */
+#define QB_CFLAG_HARDSTATE 0x10u     /* term / vote / committed differ from entry     */
+#define QB_CFLAG_IGNORED 0x20u       /* the action had no effect                      */
+
+enum {
+  QB_CSTAT_PRE_CAMPAIGNS = 0,        /* becomePreCandidate calls                  */
+  QB_CSTAT_CAMPAIGNS = 1,            /* becomeCandidate calls                     */
+  QB_CSTAT_BECAME_LEADER = 2,        /* becomeLeader calls                        */
+  QB_CSTAT_BECAME_FOLLOWER = 3,      /* becomeFollower calls                      */
+  QB_CSTAT_VOTE_REQUESTS = 4,        /* vote requests (set bits of req_mask)      */
+  QB_CSTAT_IGNORED_LEADER = 5,       /* hup at a leader                           */
+  QB_CSTAT_IGNORED_UNPROMOTABLE = 6, /* hup at a node that is not promotable      */
+  QB_CSTAT_IGNORED_PENDING_CONF = 7, /* hup under QB_CAMP_PENDING_CONF            */
+  QB_CSTAT_IGNORED_ROLE = 8,         /* WON / LOST at a follower or leader        */
+  QB_CSTAT_BAD_ACTION = 9,           /* action code above QB_CAMP_LOST            */
+  QB_CSTAT_COUNT = 10
+};
+
+/* The arrays are those of qb_leader_groups, qb_tick_groups and
+ * qb_follower_groups (same layouts: a caller passes the same buffers) plus
+ * self_id and the votes word of qb_dev_record_votes. */
+typedef struct qb_campaign_groups {
+  uint64_t G;
+  uint32_t pre_vote;           /* raft.preVote: 0 / 1                         */
+  uint32_t reserved;           /* 0                                           */
+  const uint32_t* off;         /* [G+1] */
+  const uint32_t* cfg;         /* [G] */
+  uint32_t* meta;              /* [G] in/out: bits 8-15 and 20-24 may change  */
+  const uint64_t* self_id;     /* [G] the node's raft ID                      */
+  uint64_t* term;              /* [G] in/out */
+  uint64_t* vote;              /* [G] in/out */
+  uint64_t* lead;              /* [G] in/out */
+  uint64_t* committed;         /* [G] in/out */
+  const uint64_t* last_index;  /* [G] */
+  const uint64_t* last_term;   /* [G] (the requests' LogTerm; not read here)  */
+  uint8_t* role;               /* [G] in/out: QB_ROLE_*                       */
+  uint32_t* election_elapsed;  /* [G] in/out */
+  uint32_t* heartbeat_elapsed; /* [G] in/out */
+  uint32_t* votes;             /* [G] in/out: voted | granted << 16           */
+  /* per slot, S = off[G] (in/out; written only by reset) */
+  uint64_t* match;
+  uint64_t* next;
+  uint64_t* pending_snapshot;
+  uint8_t* pstate;
+  uint32_t* infl_pos;
+} qb_campaign_groups;
+
+/* cflags [G] (QB_CFLAG_*) and req_type [G] (0 = no request) are written for
+ * every group; req_term / req_mask only where req_type is non-zero.  stats:
+ * QB_CSTAT_COUNT device uint64 (accumulated).  G == 0 is QB_OK and writes
+ * nothing; everything else is required.  No workspace and no allocation
+ * inside the call (it can be graph-captured); nothing outside the caller's
+ * arrays is read or written. */
+int qb_dev_campaign(const qb_campaign_groups* cg, const uint8_t* action, uint8_t* cflags,
+                    uint8_t* req_type, uint64_t* req_term, uint16_t* req_mask, uint64_t* stats,
+                    void* stream);
 
 /* ----------------------------------------------------------------------- */
 /* Wire ingest                                       */

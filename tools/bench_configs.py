@@ -1165,6 +1165,172 @@ def follower_config(G, reps, *, reporter=None):
     assert ok_h and ok_s, "follower parity failed"
 
 
+def campaign_config(G, reps, *, reporter=None):
+    """The batched campaign (qb_dev_campaign): G five-voter groups of the
+    synth_streaming table held by a follower (own slot 0), PreVote on.
+    Sample (a): every group gets QB_CAMP_HUP — becomePreCandidate, own vote,
+    four MsgPreVote: group words only, no slot phase.  Sample (b): every
+    group is a candidate and gets QB_CAMP_WON — becomeLeader + bcastAppend:
+    reset rewrites all five slots.  One HIP event pair per call, median over
+    the samples after warm-up; role, lead and votes are restored between
+    samples outside the timed call.  Parity: one more call at the same size
+    with seeded roles, promotable bits, terms and actions, every 1024th
+    group against tests/campaign_ref.py."""
+    reporter = reporter or report
+    import ctypes as C
+    import importlib
+    import time
+    from etcd_amd import _lib
+    from etcd_amd.quorum import tick as qt
+    from etcd_amd.quorum.leader import _to_np, synth_streaming
+    from tests import campaign_pack as P, campaign_ref as R
+    qc = importlib.import_module("etcd_amd.quorum.campaign")
+    n = 5
+    lg, _ = synth_streaming(G, W=1, D=1, n=n, device=dev)
+    S = lg.S
+    z32 = lambda: torch.zeros(G, dtype=torch.int32, device=dev)  # noqa: E731
+    state = qt.TickState(torch.full((G,), qt.ROLE_FOLLOWER | qt.ROLE_PROMOTABLE, dtype=torch.uint8,
+                                    device=dev), z32(), z32(),
+                         torch.full((G,), 15, dtype=torch.int32, device=dev))
+    lg.t["meta"].fill_(0xFF00 | (1 << 16))  # own slot 0, no transferee, one term run
+    es = qc.ElectionState.for_table(lg, state, np.arange(1, G + 1, dtype=np.uint64),
+                                    np.zeros(G, np.uint64), np.zeros(G, np.uint64),
+                                    np.full(G, 7, np.uint64), 10, True, True)
+    action = torch.zeros(G, dtype=torch.uint8, device=dev)
+    out = lg.campaign(es, action)   # (the mirror's argument checks, once; all QB_CAMP_NONE)
+    sp = torch.cuda.current_stream(dev).cuda_stream
+    ft = es.follower.t
+    cg = qc.CampaignGroupsC(
+        G=G, pre_vote=1, reserved=0, self_id=es.self_id.data_ptr(), votes=es.votes.data_ptr(),
+        role=state.role.data_ptr(), election_elapsed=state.election_elapsed.data_ptr(),
+        heartbeat_elapsed=state.heartbeat_elapsed.data_ptr(),
+        **{k: lg.t[k].data_ptr() for k in ("off", "cfg", "meta", "match", "next",
+                                           "pending_snapshot", "pstate", "infl_pos")},
+        **{k: ft[k].data_ptr() for k in ("term", "vote", "lead", "committed", "last_index",
+                                         "last_term")})
+    fn = _lib.fn("qb_dev_campaign")
+    args = (C.byref(cg), action.data_ptr(), out.cflags.data_ptr(), out.req_type.data_ptr(),
+            out.req_term.data_ptr(), out.req_mask.data_ptr(), out.stats.data_ptr(), sp)
+
+    def call():
+        _lib.check(fn(*args), "qb_dev_campaign")
+    term0 = ft["term"].clone()
+
+    def timed(role, act):
+        def restore():
+            state.role.fill_(role | qt.ROLE_PROMOTABLE)
+            ft["lead"].zero_()
+            ft["vote"].zero_()
+            ft["term"].copy_(term0)
+            es.votes.zero_()
+            action.fill_(act)
+
+        def sample(ev):
+            restore()
+            torch.cuda.synchronize()
+            ev.record(ev.ev[0], sp)
+            call()
+            ev.record(ev.ev[1], sp)
+            torch.cuda.synchronize()
+            return ev.elapsed_ms(0, 1) / 1e3
+        ev = HipEvents(2)
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < 0.3:  # warm-up: clocks settle (time_region)
+            sample(ev)
+        out.stats.zero_()
+        per = [sample(ev) for _ in range(reps)]
+        ev.close()
+        return float(np.median(per)), out.stats_dict()
+    t_hup, st = timed(qt.ROLE_FOLLOWER, qc.CAMP_HUP)
+    assert st["pre_campaigns"] == reps * G and st["vote_requests"] == reps * G * (n - 1), st
+    assert st["campaigns"] == 0 and st["became_leader"] == 0, st
+    t_won, st = timed(qt.ROLE_CANDIDATE, qc.CAMP_WON)
+    assert st["became_leader"] == reps * G and st["vote_requests"] == 0, st
+    # per group, read by every acting group: action 1, role 1, meta 4, cfg 4,
+    # off 4, term / vote / committed / self_id / last_index 40 = 54 B.
+    # (a) writes votes 4, role 1, lead 8, cflags 1, req_type 1, req_term 8,
+    # req_mask 2 = 25 B; (b) writes both counters 8, votes 4, role 1, lead 8,
+    # cflags 1, req_type 1 = 23 B (meta, term, vote and committed do not
+    # change here) and per slot match 8, next 8, pending_snapshot 8, pstate 1,
+    # infl_pos 4 = 29 B
+    hup_b = 54 + 25
+    won_b = 54 + 23 + n * 29
+    extra = {"unit": "groups/s", "samples": reps, "pre_vote": 1,
+             "hup_us": t_hup * 1e6, "hup_bytes_per_group": hup_b,
+             "hup_TBs": G * hup_b / t_hup / 1e12,
+             "hup_frac": G * hup_b / t_hup / 1e9 / HBM_PEAK_GBS,
+             "won_us": t_won * 1e6, "won_bytes_per_group": won_b,
+             "won_TBs": G * won_b / t_won / 1e12,
+             "won_frac": G * won_b / t_won / 1e9 / HBM_PEAK_GBS,
+             "timing": "one HIP event pair per call, median over the samples; per_launch_us = "
+                       "sample (b), every group WON as candidate (reset + bcastAppend)"}
+    # parity at this size
+    gen = torch.Generator(device=dev).manual_seed(0xCA3F)
+    rnd = lambda hi, k: torch.randint(0, hi, (k,), generator=gen, device=dev)  # noqa: E731
+    state.role.copy_((rnd(4, G) | (torch.where(rnd(8, G) == 0, 0, 1) << 7)).to(torch.uint8))
+    ft["term"].copy_(term0 + rnd(3, G))
+    ft["vote"].copy_(rnd(3, G))
+    ft["lead"].copy_(rnd(3, G))
+    es.votes.copy_((rnd(32, G) * 0x10001).to(torch.int32))
+    state.election_elapsed.copy_(rnd(20, G).to(torch.int32))
+    state.heartbeat_elapsed.copy_(rnd(3, G).to(torch.int32))
+    lg.t["meta"].copy_((lg.t["meta"] & ~0xFFFF | rnd(n + 1, G)
+                        | torch.where(rnd(4, G) == 0, rnd(n, G), torch.full((G,), 0xFF, device=dev))
+                        << 8).to(torch.int32))
+    action.copy_((rnd(5, G) | (torch.where(rnd(4, G) == 0, 1, 0) << 7)).to(torch.uint8))
+    sub = np.arange(0, G, 1024)
+    slots = (sub[:, None] * n + np.arange(n)[None, :]).ravel()
+
+    def gather():
+        a = {k: _to_np(lg.t[k], dt)[sub].copy() for k, dt in (
+            ("cfg", np.uint32), ("meta", np.uint32), ("term", np.uint64), ("committed", np.uint64),
+            ("last_index", np.uint64))}
+        a.update({k: _to_np(lg.t[k], dt)[slots].copy() for k, dt in (
+            ("match", np.uint64), ("next", np.uint64), ("pending_snapshot", np.uint64),
+            ("pstate", np.uint8), ("infl_pos", np.uint32), ("infl_buf", np.uint64))})
+        a["off"] = np.arange(len(sub) + 1, dtype=np.uint32) * n
+        a.update({k: np.zeros(0, dt) for k, dt in (("rq_ctx", np.uint64), ("rq_index", np.uint64),
+                                                   ("rq_meta", np.uint32))})
+        e = {k: v[sub].copy() for k, v in es.numpy().items()}
+        return a, e
+    a0, e0 = gather()
+    nodes = [P.make_node(n, int(a0["cfg"][i]) & 0xFFFF, int(a0["cfg"][i]) >> 16,
+                         int(a0["meta"][i]) & 0xFF, self_id=int(e0["self_id"][i]),
+                         last_index=int(a0["last_index"][i]), last_term=int(e0["last_term"][i]))
+             for i in range(len(sub))]
+    P.unpack_into(nodes, a0, e0, 0, 1)   # (this table's rings hold one entry)
+    fill = P.FILL - (1 << 64)
+    out.req_term.fill_(fill)
+    out.req_mask.fill_(0xA5A5 - (1 << 16))
+    out.stats.zero_()
+    act_h = action.cpu().numpy()
+    call()
+    torch.cuda.synchronize()
+    rterm, rmask = np.full(len(sub), P.FILL, np.uint64), np.full(len(sub), 0xA5A5, np.uint16)
+    cf, rt, _ = P.ref_campaign(nodes, act_h[sub], True, rterm, rmask)
+    want_a, want_e = P.pack_nodes(nodes, 0, 1)
+    a1, e1 = gather()
+    keys = ("meta", "term", "committed", "match", "next", "pending_snapshot", "pstate", "infl_pos",
+            "infl_buf")
+    ok = (all(np.array_equal(a1[k], want_a[k]) for k in keys)
+          and all(np.array_equal(e1[k], want_e[k]) for k in want_e)
+          and np.array_equal(out.cflags.cpu().numpy()[sub], cf)
+          and np.array_equal(out.req_type.cpu().numpy()[sub], rt)
+          and np.array_equal(_to_np(out.req_term, np.uint64, G)[sub], rterm)
+          and np.array_equal(_to_np(out.req_mask, np.uint16, G)[sub], rmask))
+    st = out.stats_dict()
+    ok = ok and sum(st[k] for k in ("pre_campaigns", "became_leader", "became_follower",
+                                    "ignored_leader", "ignored_pending_conf", "ignored_role")) > 0
+    extra["parity"] = bool(ok)
+    extra["parity_check"] = (f"tests/campaign_ref.py over {len(sub)} groups (every 1024th) of the "
+                             f"{G} with seeded roles, own slots, terms, votes and actions: state, "
+                             f"Progress, cflags and req_* (untouched elements included); the "
+                             f"call's stats: {st}")
+    reporter("campaign (MsgHup pre-campaign; WON: becomeLeader + bcastAppend)", G, t_won,
+             G * won_b, extra)
+    assert ok, "campaign parity failed"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -1206,6 +1372,8 @@ def main():
         tick_config(1 << 22, a.reps)
     if "follower" in which:
         follower_config(1 << 22, a.reps)
+    if "campaign" in which:
+        campaign_config(1 << 22, a.reps)
     if "wire-tracker" in which:
         wire_tracker_config(1 << 24, a.reps)
     if "wire-tracker-fused" in which:  # development A/B: the one call alone
