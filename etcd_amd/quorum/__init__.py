@@ -21,7 +21,8 @@ from .batch import INDEX_INF
 # (campaign the function takes the submodule's name here, as the call is named
 # in the header; the submodule stays importable as etcd_amd.quorum.campaign)
 from .campaign import CampaignResult, ElectionState, campaign
-from .follower import FollowerGroups, FollowerInbox, FollowerResult, follower_step
+from .follower import (FollowerAppInbox, FollowerGroups, FollowerInbox, FollowerLog,
+                       FollowerLogResult, FollowerResult, follower_log_step, follower_step)
 from .tick import TickResult, TickState, leader_tick
 
 MAX_UINT64 = INDEX_INF
@@ -177,7 +178,7 @@ def vote_results(configs: Sequence[JointConfig], votes: Sequence[Mapping[int, bo
     return [VoteResult(int(x)) for x in out]
 
 
-__all__ = ["AckedIndexer", "CampaignResult", "ElectionState", "FollowerGroups", "FollowerInbox", "FollowerResult", "INDEX_INF",
+__all__ = ["AckedIndexer", "CampaignResult", "ElectionState", "FollowerAppInbox", "FollowerGroups", "FollowerInbox", "FollowerLog", "FollowerLogResult", "FollowerResult", "INDEX_INF",
            "JointConfig", "MAX_UINT64", "MajorityConfig", "MapAckIndexer", "TickResult",
-           "TickState", "VoteLost", "VotePending", "VoteResult", "VoteWon", "batch", "campaign", "committed_indexes", "follower_step", "index_string", "leader_tick",
+           "TickState", "VoteLost", "VotePending", "VoteResult", "VoteWon", "batch", "campaign", "committed_indexes", "follower_log_step", "follower_step", "index_string", "leader_tick",
            "vote_results"]

@@ -874,6 +874,127 @@ int qb_dev_follower_step(const qb_follower_groups* fg, const qb_follower_inbox* 
                          size_t workspace_bytes, void* stream);
 
 /* ----------------------------------------------------------------------- */
+/* Follower log step: the follower step plus MsgApp                        */
+/* ----------------------------------------------------------------------- */
+
+/* qb_dev_follower_step with one more record kind, QB_FIN_APP (pb.MsgApp): the
+ * receiving side of qb_dev_leader_step's QB_MSG_APP.  Kinds 0-4 behave exactly
+ * as above and all kinds of a group are stepped in one batch order, so a vote
+ * request or a heartbeat behind an append sees the log it left.  The entries'
+ * bytes stay the host's: the call decides accept or reject, where the append
+ * starts, the log's new end and term index, the commit and the response.
+ *
+ * The log is its term index, as for the leader: the terms of
+ * [first_index - 1, last_index] as up to QB_LEADER_MAX_RUNS runs (run-major;
+ * the count in bits 16-19 of meta).  Run 0 starts at first_index - 1 (the
+ * dummy entry), starts ascend, the last run's term is last_term, adjacent
+ * runs differ in term, and first_index - 1 <= committed.  (The table is not
+ * checked on the device; etcd_amd/quorum/follower.py checks it on the host.
+ * Whatever it holds, nothing outside the caller's arrays is touched.)
+ *
+ * A QB_FIN_APP record: index = Message.Index, aux = Message.LogTerm,
+ * commit[i] = Message.Commit, and the entries, which have the indexes
+ * Index + 1, Index + 2, ..., run-length encoded by term in ent_term /
+ * ent_len[ent_off[i] .. ent_off[i + 1]).  A message whose entries are not
+ * consecutive from Index + 1 is the decoder's to send as QB_FIN_HOST.
+ *
+ * Term filter (raft.go:849-920): a higher term runs becomeFollower(m.Term,
+ *   m.From) (raft.go:876-877); a lower term with check_quorum || pre_vote is
+ *   answered with MsgAppResp, Term = term[g], resp_index 0 (raft.go:884, 906;
+ *   QB_FSTAT_STALE_ANSWERED), any other lower term is ignored.
+ * By role at or above the term: a leader ignores it (stepLeader has no case
+ *   for it; QB_FSTAT_ROLE_IGNORED), a (pre-)candidate runs
+ *   becomeFollower(m.Term, m.From) (raft.go:1390-1392), a follower sets
+ *   election_elapsed = 0 and lead = From (raft.go:1433-1435).
+ * handleAppendEntries (raft.go:1475-1511):
+ *   Index < committed: MsgAppResp{Index: committed}.
+ *   Accept, matchTerm(Index, LogTerm) (log.go:320-326; term() is 0 outside
+ *     [first_index - 1, last_index], log.go:268-274): lastnewi = Index +
+ *     number of entries; ci = findConflict (log.go:130-141), evaluated a run
+ *     at a time.  ci != 0: the log is truncated behind ci - 1 and takes the
+ *     entries from ci on (log.go:96-101, unstable.truncateAndAppend): runs
+ *     starting at or after ci are dropped, the message's runs from ci on are
+ *     appended, a run whose term equals the term before it is merged into
+ *     it; last_index := lastnewi, last_term := the last entry's term, the
+ *     run count in meta updated, app_from[i] = ci, QB_FFLAG_APPENDED.  Then
+ *     committed := max(committed, min(Commit, lastnewi)) (log.go:103,
+ *     236-244) and MsgAppResp{Index: lastnewi}.
+ *   Reject (raft.go:1496-1509): hint = findConflictByTerm(min(Index,
+ *     last_index), LogTerm) (log.go:150-171); resp_index = Index,
+ *     QB_FRESP_REJECT, resp_hint = hint, resp_log_term = term(hint).
+ *   resp_term = term[g] behind the filter, as send stamps it.
+ * Four more stops, each found before anything of the record is applied (the
+ * term filter's effect included), each with stop_at[g] = the record:
+ *   QB_FFLAG_LOG_CONFLICT: 0 < ci <= committed (Go panics, log.go:94-95), or
+ *     ci > last_index + 1: the append would leave a gap
+ *     (unstable.truncateAndAppend's slice bounds) — where a zero LogTerm or
+ *     entry term "matching" outside the log ends up;
+ *   QB_FFLAG_LOG_RUNS: the table behind the append would hold more than
+ *     QB_LEADER_MAX_RUNS runs (the host compacts, or steps the message);
+ *   QB_FFLAG_COMMIT_RANGE: commitTo's range panic (log.go:239-241) against
+ *     the last index the record would leave.
+ * Index arithmetic wraps as Go's uint64 does.
+ *
+ * resp_index[i] and app_from[i] are written for every record (0: none);
+ * resp_hint[i] / resp_log_term[i] only with a rejected MsgAppResp.  The host
+ * applies app_from in batch order. */
+#define QB_FIN_APP 5                 /* pb.MsgApp; accepted by qb_dev_follower_log_step only */
+#define QB_FFLAG_LOG_CONFLICT 0x20u  /* stopped: the append is one Go panics on          */
+#define QB_FFLAG_LOG_RUNS     0x40u  /* stopped: the append needs a 9th term run         */
+#define QB_FFLAG_APPENDED     0x80u  /* the log changed: entries to persist before the
+                                        responses may be sent                            */
+
+/* stats of the log step: QB_FSTAT_* (same meaning) and five more. */
+enum {
+  QB_FLSTAT_APP_ACCEPTED = 11,     /* MsgApp accepted (maybeAppend ok)           */
+  QB_FLSTAT_APP_REJECTED = 12,     /* MsgApp rejected with a hint                */
+  QB_FLSTAT_APP_BELOW_COMMIT = 13, /* Index < committed                          */
+  QB_FLSTAT_ENTRIES_APPENDED = 14, /* entries the logs took (lastnewi - ci + 1)  */
+  QB_FLSTAT_APP_TRUNCATED = 15,    /* appends that started at or below lastIndex */
+  QB_FLSTAT_COUNT = 16
+};
+
+typedef struct qb_follower_log {
+  uint32_t* meta;              /* [G] in/out: only bits 16-19 (term runs, 1..8) may change;
+                                  0 is read as 1, above 8 as 8                              */
+  const uint64_t* first_index; /* [G] raftLog.firstIndex()                                  */
+  uint64_t* last_index;        /* [G] in/out; must be fg->last_index (same pointer)         */
+  uint64_t* last_term;         /* [G] in/out; must be fg->last_term                         */
+  uint64_t* run_start;         /* [QB_LEADER_MAX_RUNS * G] in/out, run-major as qb_leader_groups:
+                                  run 0 starts at first_index - 1, ascending, last run's
+                                  term == last_term                                          */
+  uint64_t* run_term;          /* same layout                                                */
+} qb_follower_log;
+
+typedef struct qb_follower_app_inbox {   /* beside qb_follower_inbox, same M */
+  const uint64_t* commit;   /* [M] Message.Commit (used for QB_FIN_APP only)                 */
+  const uint32_t* ent_off;  /* [M+1] record i's entries, run-length encoded by term:
+                               runs ent_off[i] .. ent_off[i+1]; offsets above E read as E   */
+  const uint64_t* ent_term; /* [E] Entry.Term of the run                                     */
+  const uint32_t* ent_len;  /* [E] entries in the run (0: skipped)                           */
+  uint64_t E;
+} qb_follower_app_inbox;
+
+typedef struct qb_follower_app_out {
+  uint64_t* resp_index;    /* [M] Message.Index of the response; written for every record (0 if none) */
+  uint64_t* resp_hint;     /* [M] RejectHint; written only with a rejected MsgAppResp         */
+  uint64_t* resp_log_term; /* [M] LogTerm of the hint; same                                   */
+  uint64_t* app_from;      /* [M] first index the host's log takes from this message, 0 = none;
+                              written for every record                                        */
+} qb_follower_app_out;
+
+/* stats: QB_FLSTAT_COUNT device uint64 (accumulated).  The conventions are
+ * qb_dev_follower_step's: G == 0 or M == 0 is QB_OK, no allocation inside the
+ * call, nothing outside the caller's arrays is read or written.  The
+ * grouping is the follower step's and so is the workspace: its size is
+ * qb_follower_workspace_bytes(G, M), there is no second size function. */
+int qb_dev_follower_log_step(const qb_follower_groups* fg, const qb_follower_log* lg,
+                             const qb_follower_inbox* in, const qb_follower_app_inbox* app,
+                             uint8_t* resp_type, uint64_t* resp_term, const qb_follower_app_out* out,
+                             uint32_t* stop_at, uint8_t* gflags, uint64_t* stats,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* ----------------------------------------------------------------------- */
 /* Campaign: MsgHup and election outcomes                                  */
 /* ----------------------------------------------------------------------- */
 

@@ -1165,6 +1165,212 @@ def follower_config(G, reps, *, reporter=None):
     assert ok_h and ok_s, "follower parity failed"
 
 
+def follower_log_config(G, reps, *, reporter=None):
+    """The batched follower log step (qb_dev_follower_log_step): G follower
+    groups (term 7, leader 1 known, CheckQuorum and PreVote on, ElectionTick
+    10), each log [last - 100, last] of term 7 (one term run), committed 50
+    below its end.  (a) steady replication: M = G same-term MsgApp in shuffled
+    arrival order, each at Index = last_index with one run of 64 entries of
+    term 7 and Commit 32 past the old end: every group appends, commits and
+    answers, and no record reads or writes the run table.  (b) the same plus
+    one heartbeat per group behind its MsgApp (Commit 48 past the old end: in
+    range only with the new lastIndex), M = 2 G.  The state is restored
+    between samples, outside the timed call.  Parity at this size:
+    tests/append_ref.py over the records of every 1024th group (4096 groups;
+    exact, because groups are independent) — their state, log, responses,
+    app_from, gflags and stop_at after one call of each sample."""
+    reporter = reporter or report
+    import ctypes as C
+    from etcd_amd import _lib
+    from etcd_amd.quorum import follower as qf, tick as qt
+    from etcd_amd.quorum.leader import _to_np
+    from tests import append_ref as A, follower_ref as F
+    ET, TERM, ENTS = 10, 7, 64
+    i64 = lambda v: torch.full((G,), v, dtype=torch.int64, device=dev)  # noqa: E731
+    g = torch.arange(G, dtype=torch.int64, device=dev)
+    last = 5096 + (g * 37) % 1000
+    t = {"term": i64(TERM), "vote": i64(1), "lead": i64(1), "committed": last - 50,
+         "last_index": last.clone(), "last_term": i64(TERM)}
+    state = qt.TickState(torch.full((G,), qt.ROLE_PROMOTABLE, dtype=torch.uint8, device=dev),
+                         torch.ones(G, dtype=torch.int32, device=dev),
+                         torch.zeros(G, dtype=torch.int32, device=dev),
+                         torch.full((G,), 15, dtype=torch.int32, device=dev))
+    fg = qf.FollowerGroups(G, ET, True, True, t, state)
+    run_start = torch.zeros(qf.MAX_RUNS * G, dtype=torch.int64, device=dev)
+    run_term = torch.zeros(qf.MAX_RUNS * G, dtype=torch.int64, device=dev)
+    run_start[:G] = last - 100
+    run_term[:G] = TERM
+    lg = qf.FollowerLog(G, torch.full((G,), 1 << 16, dtype=torch.int32, device=dev), last - 99,
+                        run_start, run_term)
+    lg.validate(fg)
+    pristine = {k: v.clone() for k, v in t.items()}
+    pristine_log = (lg.meta.clone(), run_start.clone(), run_term.clone())
+
+    def sample(per_group):
+        """per_group records per group in shuffled arrival order; the group's
+        first is its MsgApp, the second (if any) its heartbeat."""
+        M = per_group * G
+        sg = torch.randperm(M, device=dev) % G
+        order = torch.argsort(sg, stable=True)
+        rank = torch.empty_like(order)
+        rank[order] = torch.arange(M, device=dev) % per_group
+        is_app = rank == 0
+        ib = qf.FollowerInbox(sg.to(torch.int32),
+                              torch.where(is_app, qf.FIN_APP, qf.FIN_HEARTBEAT).to(torch.uint8),
+                              torch.ones_like(sg), torch.full_like(sg, TERM),
+                              torch.where(is_app, last[sg], last[sg] + 48),
+                              torch.where(is_app, TERM, 0))
+        ib._m = M
+        off = torch.zeros(M + 1, dtype=torch.int64, device=dev)
+        off[1:] = torch.cumsum(is_app.to(torch.int64), 0)
+        app = qf.FollowerAppInbox(torch.where(is_app, last[sg] + 32, 0), off.to(torch.int32),
+                                  i64(TERM), torch.full((G,), ENTS, dtype=torch.int32, device=dev), G)
+        return ib, app
+    sp = torch.cuda.current_stream(dev).cuda_stream
+    fgc = qf.FollowerGroupsC(G=G, election_timeout=ET, check_quorum=1, pre_vote=1, reserved=0,
+                             role=state.role.data_ptr(),
+                             election_elapsed=state.election_elapsed.data_ptr(),
+                             heartbeat_elapsed=state.heartbeat_elapsed.data_ptr(),
+                             **{k: v.data_ptr() for k, v in t.items()})
+    lgc = qf.FollowerLogC(meta=lg.meta.data_ptr(), first_index=lg.first_index.data_ptr(),
+                          last_index=t["last_index"].data_ptr(), last_term=t["last_term"].data_ptr(),
+                          run_start=run_start.data_ptr(), run_term=run_term.data_ptr())
+    fn = _lib.fn("qb_dev_follower_log_step")
+
+    def restore():
+        for k, v in pristine.items():
+            t[k].copy_(v)
+        lg.meta.copy_(pristine_log[0])
+        run_start.copy_(pristine_log[1])
+        run_term.copy_(pristine_log[2])
+        state.role.fill_(qt.ROLE_PROMOTABLE)
+        state.election_elapsed.fill_(1)
+        state.heartbeat_elapsed.zero_()
+
+    def caller(ib, app, res):
+        ibc = qf.FollowerInboxC(M=ib.M, group=ib.group.data_ptr(), flags=ib.flags.data_ptr(),
+                                term=ib.term.data_ptr(), index=ib.index.data_ptr(),
+                                aux=ib.aux.data_ptr())
+        setattr(ibc, "from", ib.frm.data_ptr())
+        apc = qf.FollowerAppInboxC(commit=app.commit.data_ptr(), ent_off=app.ent_off.data_ptr(),
+                                   ent_term=app.ent_term.data_ptr(), ent_len=app.ent_len.data_ptr(),
+                                   E=app.E)
+        aoc = qf.FollowerAppOutC(resp_index=res.resp_index.data_ptr(),
+                                 resp_hint=res.resp_hint.data_ptr(),
+                                 resp_log_term=res.resp_log_term.data_ptr(),
+                                 app_from=res.app_from.data_ptr())
+        args = (C.byref(fgc), C.byref(lgc), C.byref(ibc), C.byref(apc), res.resp_type.data_ptr(),
+                res.resp_term.data_ptr(), C.byref(aoc), res.stop_at.data_ptr(),
+                res.gflags.data_ptr(), res.stats.data_ptr(), res.workspace.data_ptr(),
+                res.workspace.numel() * 8, sp)
+        keep = (ibc, apc, aoc)
+        return lambda: (keep, _lib.check(fn(*args), "qb_dev_follower_log_step"))
+
+    def timed(call, n):
+        ev = HipEvents(2)
+        ts = []
+        for _ in range(n):
+            restore()
+            torch.cuda.synchronize()
+            ev.record(ev.ev[0], sp)
+            call()
+            ev.record(ev.ev[1], sp)
+            torch.cuda.synchronize()
+            ts.append(ev.elapsed_ms(0, 1) / 1e3)
+        ev.close()
+        return ts
+
+    def parity(ib, app, call, res):
+        restore()
+        res.stats.zero_()
+        torch.cuda.synchronize()
+        grp = _to_np(ib.group, np.uint32, ib.M)
+        sel = np.flatnonzero(grp % 1024 == 5)
+        sub = np.unique(grp[sel])
+        before = {k: _to_np(v, np.uint64, G)[sub].copy() for k, v in t.items()}
+        sb = {k: v[sub].copy() for k, v in state.numpy(G).items()}
+        first = _to_np(lg.first_index, np.uint64, G)[sub]
+        cols = {k: _to_np(getattr(ib, k), dt, ib.M)[sel] for k, dt in (
+            ("flags", np.uint8), ("frm", np.uint64), ("term", np.uint64), ("index", np.uint64),
+            ("aux", np.uint64))}
+        commit = _to_np(app.commit, np.uint64, ib.M)[sel]
+        call()
+        torch.cuda.synchronize()
+        nodes = []
+        for j in range(len(sub)):
+            n = A.new_node([TERM] * (int(before["last_index"][j]) - int(first[j]) + 2), int(first[j]),
+                           term=int(before["term"][j]), vote=int(before["vote"][j]),
+                           lead=int(before["lead"][j]), committed=int(before["committed"][j]),
+                           role=int(sb["role"][j]), election_elapsed=int(sb["election_elapsed"][j]),
+                           heartbeat_elapsed=int(sb["heartbeat_elapsed"][j]))
+            assert n.last_index == int(before["last_index"][j])
+            nodes.append(n)
+        where = {int(gg): j for j, gg in enumerate(sub)}
+        recs = []
+        for k, i in enumerate(sel):
+            kind = int(cols["flags"][k]) & 7
+            a = (kind, int(cols["frm"][k]), int(cols["term"][k]), int(cols["index"][k]),
+                 int(cols["aux"][k]), False)
+            recs.append((where[int(grp[i])],
+                         A.AppRec(*a, int(commit[k]), [TERM] * ENTS) if kind == A.APP else F.Rec(*a)))
+        o = A.step_batch(nodes, recs, F.Config(ET, True, True))
+        stop = [int(sel[s]) if s != F.NO_STOP else s for s in o["stop_at"]]
+        after = fg.numpy()
+        ok = all(np.array_equal(after[k][sub], np.array([getattr(n, k) for n in nodes],
+                                                        after[k].dtype)) for k in after)
+        la = lg.numpy()
+        ok = ok and all(A.runs_of(n.terms, n.first_index) ==
+                        ([int(la["run_start"][0, gg])], [int(la["run_term"][0, gg])])
+                        and int(la["meta"][gg]) == 1 << 16 for n, gg in zip(nodes, sub))
+        for k, dt in (("resp_type", np.uint8), ("resp_term", np.uint64), ("resp_index", np.uint64),
+                      ("app_from", np.uint64)):
+            ok = ok and np.array_equal(_to_np(getattr(res, k), dt, ib.M)[sel], np.array(o[k], dt))
+        ok = (ok and np.array_equal(_to_np(res.stop_at, np.uint32, G)[sub], np.array(stop, np.uint32))
+              and np.array_equal(_to_np(res.gflags, np.uint8, G)[sub], np.array(o["gflags"], np.uint8)))
+        return bool(ok), len(sub), len(sel)
+
+    out = {}
+    for what, per_group in (("app", 1), ("app_hb", 2)):
+        ib, app = sample(per_group)
+        restore()
+        res = qf.follower_log_step(fg, lg, ib, app)   # (the mirror's argument checks, once)
+        call = caller(ib, app, res)
+        timed(call, 5)                                # warm-up
+        res.stats.zero_()
+        tm = float(np.median(timed(call, reps)))
+        st = res.stats_dict()
+        assert st["app_accepted"] == reps * G and st["entries_appended"] == reps * G * ENTS, st
+        assert st["heartbeats"] == (per_group - 1) * reps * G and st["after_stop"] == 0, st
+        out[what] = (tm,) + parity(ib, app, call, res)
+    # arithmetic bytes (not counters).  MsgApp, per record: group 4, flags 1,
+    # from 8, term 8, Index 8, LogTerm 8, Commit 8, ent_off 2 x 4, the run's
+    # term 8 and length 4 in; resp_type 1, resp_term 8, resp_index 8, app_from
+    # 8 out = 98.  Per group: term 8, vote 8, lead 8, last_term 8, role 1 in;
+    # committed and last_index 8 in + 8 out each, electionElapsed 4 + 4,
+    # gflags 1, stop_at 4 = 78.  The heartbeat behind it, per record: 4 + 1 +
+    # 8 + 8 + 8 + 8 in, Commit 8 and ent_off 8 read with every record, the four
+    # response columns 25 out = 78.
+    a_b, b_b = 98 + 78, 98 + 78 + 78
+    (t_a, ok_a, ng, nr_a), (t_b, ok_b, _, nr_b) = out["app"], out["app_hb"]
+    extra = {"unit": "groups/s", "samples": reps, "entries_per_app": ENTS,
+             "app_us": t_a * 1e6, "app_bytes_per_group": a_b,
+             "app_tbs": G * a_b / t_a / 1e12, "app_frac": G * a_b / t_a / 1e9 / HBM_PEAK_GBS,
+             "app_hb_us": t_b * 1e6, "app_hb_bytes_per_group": b_b, "app_hb_records": 2 * G,
+             "app_hb_tbs": G * b_b / t_b / 1e12,
+             "app_hb_frac": G * b_b / t_b / 1e9 / HBM_PEAK_GBS,
+             "bytes": "arithmetic (the columns a record and a group touch), not counters; the "
+                      "grouping passes' workspace traffic is not counted",
+             "election_tick": ET, "check_quorum": 1, "pre_vote": 1,
+             "parity_app": ok_a, "parity_app_hb": ok_b, "parity": bool(ok_a and ok_b),
+             "parity_check": (f"tests/append_ref.py over the records of {ng} groups (every 1024th) "
+                              f"of the {G}: {nr_a} / {nr_b} records; state, run table, meta, "
+                              "resp_type, resp_term, resp_index, app_from, stop_at and gflags"),
+             "timing": "one HIP event pair per call, median over the samples; state and log "
+                       "restored outside the timed call"}
+    reporter("follower log step (steady MsgApp; MsgApp + heartbeat)", G, t_a, G * a_b, extra)
+    assert ok_a and ok_b, "follower-log parity failed"
+
+
 def campaign_config(G, reps, *, reporter=None):
     """The batched campaign (qb_dev_campaign): G five-voter groups of the
     synth_streaming table held by a follower (own slot 0), PreVote on.
@@ -1372,6 +1578,8 @@ def main():
         tick_config(1 << 22, a.reps)
     if "follower" in which:
         follower_config(1 << 22, a.reps)
+    if "follower-log" in which:
+        follower_log_config(1 << 22, a.reps)
     if "campaign" in which:
         campaign_config(1 << 22, a.reps)
     if "wire-tracker" in which:
