@@ -135,6 +135,17 @@ __global__ __launch_bounds__(kBlock) void k_fixed(const u64* __restrict__ match,
   }
 }
 
+// Two adjacent 1-byte masks as one 2-byte load, zero-extended by the load
+// itself (no VALU work on the result).  Default cache policy: nt here measured
+// equal at 1M groups and about 3% slower at 16M.
+__device__ __forceinline__ u32 ld_pair(const u8* __restrict__ p) {
+  return *reinterpret_cast<const u16*>(p);
+}
+
+// s_waitcnt immediate (gfx9 encoding) for vmcnt(0) alone: expcnt [6:4] and
+// lgkmcnt [11:8] at their maxima, vmcnt [3:0] and [15:14] zero.
+constexpr int kWaitVmcnt0 = 0x0F70;
+
 // LDS-DMA form (CommittedIndex wanted, n <= 8, aligned operands): a
 // workgroup owns kBlock * GPT consecutive groups; each slot row's slice for
 // them (kBlock * GPT * 8 contiguous bytes) lands in LDS by
@@ -143,7 +154,8 @@ __global__ __launch_bounds__(kBlock) void k_fixed(const u64* __restrict__ match,
 // groups 2 (k kBlock + t) and +1).  Longer contiguous row slices than the
 // register form's one dwordx4 per row and lane, and no VGPRs held by the
 // loads: 1M groups 8.7-8.9 -> 8.5 us, 16M 146 -> 141 us
-// (`profiles/r02/ab_fixed_ldsdma.log`).
+// (`profiles/r02/ab_fixed_ldsdma.log`).  tests/test_fixed_lds_isa.py holds
+// the "one wait" in the ISA of every instantiation.
 template <int N, int GPT, bool VOTE>
 __global__ __launch_bounds__(kBlock) void k_fixed_lds(const u64* __restrict__ match, u64 G,
                                                       const MaskT<N>* __restrict__ voted,
@@ -154,6 +166,10 @@ __global__ __launch_bounds__(kBlock) void k_fixed_lds(const u64* __restrict__ ma
   constexpr int kPer = GPT / 2;  // 16-byte pieces per lane and row
   constexpr u32 kSpan = u32(kBlock) * GPT;
   __shared__ __attribute__((aligned(16))) u64 lds[N][kSpan];
+  // 4 workgroups per CU fill its 160 KB of LDS exactly at N = 5: one byte
+  // more and a CU holds 3.
+  static_assert(sizeof(lds) <= 40 * 1024, "k_fixed_lds landing buffer over 40 KB");
+  static_assert(sizeof(M) == 1, "mask pairs are loaded as 2 bytes");
   const u64 gb = u64(blockIdx.x) * kSpan;
   if (gb + kSpan > G) {  // the tail workgroup (block-uniform): group by group
     const u64 g0 = gb + u64(threadIdx.x) * GPT;
@@ -169,20 +185,10 @@ __global__ __launch_bounds__(kBlock) void k_fixed_lds(const u64* __restrict__ ma
     }
     return;
   }
-  M vd[GPT], gr[GPT];
-  if constexpr (VOTE) {
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-      const u64 ge = gb + 2ull * (u32(k) * kBlock + threadIdx.x);
-      M a[2], b[2];
-      vload<M, 2>(voted + ge, a);
-      vload<M, 2>(granted + ge, b);
-      vd[2 * k] = a[0];
-      vd[2 * k + 1] = a[1];
-      gr[2 * k] = b[0];
-      gr[2 * k + 1] = b[1];
-    }
-  }
+  // One memory round trip: every DMA piece, then every mask load, is issued
+  // before the single wait, and the mask pairs stay raw (not shifted, not
+  // widened) until after it -- an unpack hoisted between the issues would
+  // make the compiler wait there and split the staging in two.
   const u32 wave_base = threadIdx.x & ~63u;
 #pragma unroll
   for (int s = 0; s < N; ++s)
@@ -194,6 +200,27 @@ __global__ __launch_bounds__(kBlock) void k_fixed_lds(const u64* __restrict__ ma
           (gbl_cvoid_t*)(reinterpret_cast<const char*>(match + u64(s) * G + gb) + 16ull * piece),
           (lds_void_t*)dst, 16, 0, 2);
     }
+  u32 vd2[kPer], gr2[kPer];  // the two mask bytes of piece k's groups
+  if constexpr (VOTE) {
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
+      const u64 ge = gb + 2ull * (u32(k) * kBlock + threadIdx.x);
+      vd2[k] = ld_pair(voted + ge);
+      gr2[k] = ld_pair(granted + ge);
+    }
+  }
+  // The wave's own vmcnt(0) completes its DMAs and mask loads; the empty asm
+  // keeps every use of a mask pair below it.  Lane t reads back exactly the
+  // bytes lane t's DMA wrote (piece k of row s lands at byte 16 (k kBlock + t)
+  // of lds[s]; elements 2 (k kBlock + t), +1 are those 16 bytes), so no data
+  // crosses waves and the barrier below orders nothing the wait has not: it
+  // stays because removing it measured no gain.
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
+  if constexpr (VOTE) {
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) asm volatile("" : "+v"(vd2[k]), "+v"(gr2[k])::"memory");
+  }
   __syncthreads();
   u64 ci[GPT];
   u8 vr[GPT];
@@ -203,7 +230,9 @@ __global__ __launch_bounds__(kBlock) void k_fixed_lds(const u64* __restrict__ ma
     u64 v[N];
 #pragma unroll
     for (int s = 0; s < N; ++s) v[s] = lds[s][e];
-    eval_fixed<N, true, VOTE>(v, VOTE ? u32(vd[j]) : 0u, VOTE ? u32(gr[j]) : 0u, ci[j], vr[j]);
+    const u32 sh = 8u * u32(j & 1);
+    eval_fixed<N, true, VOTE>(v, VOTE ? (vd2[j / 2] >> sh) & 0xFFu : 0u,
+                              VOTE ? (gr2[j / 2] >> sh) & 0xFFu : 0u, ci[j], vr[j]);
   }
 #pragma unroll
   for (int k = 0; k < kPer; ++k) {

@@ -200,6 +200,128 @@ void launch_ldsdma(const u64* m, u64 G, const u8* vd, const u8* gr, u64* c, u8* 
                      vd, gr, c, v, 0ull);
 }
 
+// Staging steps of the product's k_fixed_lds<5, 4, true> (GPT = 4, 256
+// threads), one variant per step so they can be interleaved in one process:
+//   STEP 0  the kernel before the one-round-trip change: masks loaded first
+//           as two u8 (the compiler hoists an unpack above the tenth DMA and
+//           waits twice), __syncthreads();
+//   STEP 1  every DMA, then the raw 2-byte mask pairs, then one wait;
+//           __syncthreads() kept (the product kernel);
+//   STEP 2  STEP 1 with the wave's own vmcnt(0) instead of the barrier;
+//   STEP 3  STEP 2 with nt on the mask loads;
+//   STEP 4  STEP 1 with the raw mask pairs issued before the DMAs;
+//   STEP 5  STEP 1 with the DMAs issued piece-major (piece 0 of every row,
+//           then piece 1) instead of row-major.
+
+// STEP 0's mask load: the product's vload<u8, 2> of that commit.
+__device__ __forceinline__ void vload2(const u8* __restrict__ p, u8 (&out)[2]) {
+  const u16 x = __builtin_nontemporal_load(reinterpret_cast<const u16*>(p));
+  __builtin_memcpy(out, &x, 2);
+}
+
+template <int STEP>
+__global__ __launch_bounds__(256) void k_stage(const u64* __restrict__ match, u64 G,
+                                               const u8* __restrict__ voted,
+                                               const u8* __restrict__ granted,
+                                               u64* __restrict__ commit, u8* __restrict__ vote,
+                                               u64) {
+  constexpr int GPT = 4, kPer = 2, BLOCK = 256;
+  constexpr u32 kSpan = u32(BLOCK) * GPT;
+  __shared__ __attribute__((aligned(16))) u64 lds[N][kSpan];
+  const u64 gb = u64(blockIdx.x) * kSpan;
+  if (gb + kSpan > G) {
+    const u64 g0 = gb + u64(threadIdx.x) * GPT;
+    for (u64 g = g0; g < G && g < g0 + GPT; ++g) {
+      u64 v[N];
+#pragma unroll
+      for (int s = 0; s < N; ++s) v[s] = match[u64(s) * G + g];
+      commit[g] = select_quorum<N>(v);
+      vote[g] = vote5(voted[g], granted[g]);
+    }
+    return;
+  }
+  u8 vd[GPT], gr[GPT];
+  u32 vd2[kPer], gr2[kPer];
+  if constexpr (STEP == 0) {
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
+      const u64 ge = gb + 2ull * (u32(k) * BLOCK + threadIdx.x);
+      u8 a[2], b[2];
+      vload2(voted + ge, a);
+      vload2(granted + ge, b);
+      vd[2 * k] = a[0];
+      vd[2 * k + 1] = a[1];
+      gr[2 * k] = b[0];
+      gr[2 * k + 1] = b[1];
+    }
+  }
+  auto load_pairs = [&] {
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
+      const u64 ge = gb + 2ull * (u32(k) * BLOCK + threadIdx.x);
+      vd2[k] = ldT<STEP == 3>(reinterpret_cast<const u16*>(voted + ge));
+      gr2[k] = ldT<STEP == 3>(reinterpret_cast<const u16*>(granted + ge));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  if constexpr (STEP == 4) load_pairs();
+  const u32 wave_base = threadIdx.x & ~63u;
+#pragma unroll
+  for (int i = 0; i < N * kPer; ++i) {
+    // row-major issue order (both pieces of a row back to back); STEP 5: piece-major
+    const int s = STEP == 5 ? i % N : i / kPer, k = STEP == 5 ? i / N : i % kPer;
+    const u32 piece = u32(k) * BLOCK + threadIdx.x;
+    char* dst = reinterpret_cast<char*>(&lds[s][0]) + 16u * (u32(k) * BLOCK + wave_base);
+    __builtin_amdgcn_global_load_lds(
+        (gbl_cvoid_t*)(reinterpret_cast<const char*>(match + u64(s) * G + gb) + 16ull * piece),
+        (lds_void_t*)dst, 16, 0, 2);
+    if constexpr (STEP == 5) __builtin_amdgcn_sched_barrier(0);
+  }
+  if constexpr (STEP >= 1) {
+    if constexpr (STEP != 4) load_pairs();
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) alone
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) asm volatile("" : "+v"(vd2[k]), "+v"(gr2[k])::"memory");
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < GPT; ++j) {
+      vd[j] = u8(vd2[j / 2] >> (8 * (j & 1)));
+      gr[j] = u8(gr2[j / 2] >> (8 * (j & 1)));
+    }
+  }
+  if constexpr (STEP <= 1 || STEP >= 4) __syncthreads();
+  u64 ci[GPT];
+  u8 vr[GPT];
+#pragma unroll
+  for (int j = 0; j < GPT; ++j) {
+    const u32 e = 2u * (u32(j / 2) * BLOCK + threadIdx.x) + u32(j & 1);
+    u64 v[N];
+#pragma unroll
+    for (int s = 0; s < N; ++s) v[s] = lds[s][e];
+    ci[j] = select_quorum<N>(v);
+    vr[j] = vote5(vd[j], gr[j]);
+  }
+  using V = u32 __attribute__((ext_vector_type(4)));
+#pragma unroll
+  for (int k = 0; k < kPer; ++k) {
+    const u64 ge = gb + 2ull * (u32(k) * BLOCK + threadIdx.x);
+    V x;
+    x.x = u32(ci[2 * k]);
+    x.y = u32(ci[2 * k] >> 32);
+    x.z = u32(ci[2 * k + 1]);
+    x.w = u32(ci[2 * k + 1] >> 32);
+    stT<true>(reinterpret_cast<V*>(commit + ge), x);
+    stT<true>(reinterpret_cast<u16*>(vote + ge), u16(u32(vr[2 * k]) | (u32(vr[2 * k + 1]) << 8)));
+  }
+}
+
+template <int STEP>
+void launch_stage(const u64* m, u64 G, const u8* vd, const u8* gr, u64* c, u8* v, hipStream_t st) {
+  const u64 blocks = (G + 1023) / 1024;
+  hipLaunchKernelGGL((k_stage<STEP>), dim3(unsigned(blocks)), dim3(256), 0, st, m, G, vd, gr, c, v,
+                     0ull);
+}
+
 struct Variant {
   const char* name;
   void (*launch)(const u64*, u64, const u8*, const u8*, u64*, u8*, hipStream_t);
@@ -246,6 +368,12 @@ const Variant kVariants[] = {
     {"ldsdma8_b128", launch_ldsdma<8, 2, 128>},
     {"ldsdma8_nt", launch_ldsdma<8, 2, 256>},
     {"ldsdma4_aux1", launch_ldsdma<4, 1, 256>},
+    {"stage0_parent", launch_stage<0>},
+    {"stage1_onetrip", launch_stage<1>},
+    {"stage2_wavewait", launch_stage<2>},
+    {"stage3_nt", launch_stage<3>},
+    {"stage4_masksfirst", launch_stage<4>},
+    {"stage5_piecemajor", launch_stage<5>},
     {"floor_gpt4", launch_var<4, false, false, false, 256, 0>},
     {"floor_gpt2", launch_var<2, false, false, false, 256, 0>},
     {"floor_gpt2_nt", launch_var<2, true, false, false, 256, 0>},
