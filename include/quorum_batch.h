@@ -448,7 +448,8 @@ int qb_dev_csr_tally_votes(uint64_t G, const uint32_t* cfg,
  *     (read_only.go:68-121) + responseToReadIndexReq (raft.go:1737-1752);
  *   MsgSnapStatus, MsgUnreachable (raft.go:1310-1338).
  * Records of a group are applied in batch order; groups are independent.
- * The leader's log is a static view (the step never appends): firstIndex,
+ * The leader's log is a static view (this step never appends; the log grows
+ * in qb_dev_leader_propose): firstIndex,
  * lastIndex, the terms of [firstIndex-1, lastIndex] as up to
  * QB_LEADER_MAX_RUNS runs, the storage snapshot, and max_ents = the number
  * of entries raftLog.entries(lo, MaxSizePerMsg) returns (entries of one size).
@@ -1056,8 +1057,9 @@ int qb_dev_follower_log_step(const qb_follower_groups* fg, const qb_follower_log
  *   neither back); maybeCommit: committed := last_index + 1 iff that exceeds
  *   it, the config has a voter and every non-empty half is {own slot}.  The
  *   empty entry itself, last_index / last_term, the term-run table and
- *   pendingConfIndex are the log's and stay the host's
- *   (QB_CFLAG_BECAME_LEADER); the call uses last_index as it stood at entry.
+ *   pendingConfIndex are the log's: qb_dev_leader_propose's
+ *   QB_PROP_LEADER_ENTRY, or the host (QB_CFLAG_BECAME_LEADER); the call
+ *   uses last_index as it stood at entry.
  * QB_CAMP_WON as a candidate also runs bcastAppend (raft.go:515-522, 432-492)
  *   on the Progress: every slot but the own becomes QB_PR_PROBE |
  *   QB_PR_PROBE_SENT, QB_CFLAG_BCAST_APPEND, and the host forms per such
@@ -1139,6 +1141,178 @@ typedef struct qb_campaign_groups {
 int qb_dev_campaign(const qb_campaign_groups* cg, const uint8_t* action, uint8_t* cflags,
                     uint8_t* req_type, uint64_t* req_term, uint16_t* req_mask, uint64_t* stats,
                     void* stream);
+
+/* ----------------------------------------------------------------------- */
+/* Propose: MsgProp, appendEntry and bcastAppend at the leader             */
+/* ----------------------------------------------------------------------- */
+
+/* Step(MsgProp) -> appendEntry -> bcastAppend (raft.go:1019-1077, 621-642,
+ * 1761-1779, 432-522) and the log's share of becomeLeader (raft.go:745-756)
+ * for G groups in one call: the call that lets a leader's log grow on the
+ * device.  Dense, one action per group (a node receives at most one batched
+ * proposal per group and call: the host concatenates a group's MsgProps),
+ * groups independent.  The entries' bytes stay the host's; the call decides
+ * whether they are taken, which indexes they get, the log's new end and term
+ * index, the commit, and the MsgApp / MsgSnap of bcastAppend.
+ *
+ * action[g] & 0x3F:
+ *   QB_PROP_NONE          nothing (pflags[g] = 0);
+ *   QB_PROP_ENTRIES       Step(MsgProp) with n_ents[g] entries whose
+ *                         PayloadSize sum is payload[g];
+ *     | QB_PROP_CONF_CHANGE     entry cc_at[g] (0-based) is an EntryConfChange
+ *                         / EntryConfChangeV2 of cc_payload[g] bytes
+ *                         (cc_at >= n_ents reads as the bit being clear);
+ *     | QB_PROP_CC_LEAVE_JOINT  that change has no Changes (wantsLeaveJoint).
+ *                         A proposal with more than one conf-change entry
+ *                         stays the host's;
+ *   QB_PROP_LEADER_ENTRY  the log's share of becomeLeader, called after
+ *                         qb_dev_campaign reported QB_CFLAG_BECAME_LEADER;
+ *   any other code is treated as QB_PROP_NONE and counted
+ *   (QB_PSTAT_BAD_ACTION).
+ *
+ * QB_PROP_ENTRIES by role (MsgProp is local, Term 0: the term filter passes
+ * it).  A follower with lead == 0 or under disable_proposal_forwarding drops
+ * it (raft.go:1423-1430), any other follower gets QB_PFLAG_FORWARD (the host
+ * sends the message to lead[g]); a (pre-)candidate drops it (raft.go:1387-
+ * 1389).  At a leader, in this order:
+ *   1. n_ents == 0 (Go panics): QB_PFLAG_BAD, nothing applied.
+ *   2. the own slot (meta bits 0-7) is >= the group's slot count (no
+ *      Progress): dropped.
+ *   3. the transferee (meta bits 8-15) is not 0xFF: dropped.
+ *   4. last_term != term and the table already holds QB_LEADER_MAX_RUNS runs:
+ *      QB_PFLAG_LOG_RUNS, nothing applied (the host compacts the table).
+ *   5. the conf-change rule (raft.go:1050-1070): refused iff
+ *      pending_conf_index > applied, or joint (cfg >> 16 != 0) without
+ *      LEAVE_JOINT, or LEAVE_JOINT while not joint.  Refused:
+ *      QB_PFLAG_CC_REFUSED (the host replaces that entry with an empty normal
+ *      entry) and the size s below is payload - cc_payload; else
+ *      pending_conf_index := last_index + cc_at + 1, which stands even if 6
+ *      drops the proposal, as in Go.
+ *   6. increaseUncommittedSize: dropped iff uncommitted_size > 0 && s > 0 &&
+ *      uncommitted_size + s > max_uncommitted_size (the sum wraps as uint64;
+ *      a limit of 0 is no limit, as Config.validate makes it); else
+ *      uncommitted_size += s.
+ *   7. append: last_term != term adds the run (last_index + 1, term);
+ *      last_index += n_ents, last_term := term (QB_PFLAG_APPENDED: the
+ *      entries take the indexes last_index - n_ents + 1 ..).
+ *   8. MaybeUpdate(last_index) on the own slot, maybeCommit (the joint
+ *      committed index over match, > committed, its term == term:
+ *      QB_PFLAG_COMMITTED).
+ *   9. bcastAppend (QB_PFLAG_BCAST): maybeSendAppend(to, true) for every slot
+ *      but the own, exactly as qb_dev_leader_step sends (paused rule,
+ *      term(next - 1), min(max_ents, last - next + 1) entries, the MsgSnap
+ *      fallback with RecentActive and snap_index != 0, OptimisticUpdate +
+ *      Inflights.Add in Replicate, ProbeSent in Probe).  At most one message
+ *      per peer, so they are slot-indexed: msg_type[s] = 0 / QB_MSG_APP /
+ *      QB_MSG_SNAP; a MsgApp is {Index: msg_index[s], LogTerm:
+ *      msg_log_term[s], Commit: committed[g] after the call, msg_n[s]
+ *      entries from Index + 1}, a MsgSnap carries the snapshot's index and
+ *      term there.
+ * QB_PROP_LEADER_ENTRY acts only at a leader (elsewhere ignored and counted):
+ *   step 4's stop, then pending_conf_index := last_index as at entry, one
+ *   entry appended as in 7, uncommitted_size := 0.  No Progress word is
+ *   touched (qb_dev_campaign already ran MaybeUpdate(last_index + 1) and
+ *   maybeCommit) and no message is produced.
+ * The steady proposal (last_term == term, every peer's next - 1 at or past
+ * the old last index) reads and writes no run table.  Index arithmetic wraps
+ * as Go's uint64 does.  A run count of 0 in meta is read as 1, above 8 as 8;
+ * a slot count above QB_MAX_SLOTS as QB_MAX_SLOTS. */
+#define QB_PROP_NONE 0
+#define QB_PROP_ENTRIES 1
+#define QB_PROP_LEADER_ENTRY 2
+#define QB_PROP_CONF_CHANGE 0x40u
+#define QB_PROP_CC_LEAVE_JOINT 0x80u
+
+#define QB_PFLAG_APPENDED 0x01u   /* the log grew: entries to persist            */
+#define QB_PFLAG_BCAST 0x02u      /* bcastAppend ran: msg_type of the group's slots written */
+#define QB_PFLAG_COMMITTED 0x04u  /* maybeCommit returned true                   */
+#define QB_PFLAG_DROPPED 0x08u    /* ErrProposalDropped                          */
+#define QB_PFLAG_FORWARD 0x10u    /* a follower: the host sends MsgProp to lead  */
+#define QB_PFLAG_CC_REFUSED 0x20u /* the conf change becomes an empty normal entry */
+#define QB_PFLAG_LOG_RUNS 0x40u   /* stopped: the append needs a 9th term run    */
+#define QB_PFLAG_BAD 0x80u        /* stopped: an empty MsgProp (Go panics)       */
+
+enum {
+  QB_PSTAT_PROPOSALS = 0,           /* proposals appended                        */
+  QB_PSTAT_ENTRIES = 1,             /* entries appended (leader entries included) */
+  QB_PSTAT_DROP_NO_PROGRESS = 2,    /* the leader has no Progress of its own     */
+  QB_PSTAT_DROP_TRANSFER = 3,       /* a leadership transfer is in progress      */
+  QB_PSTAT_DROP_SIZE = 4,           /* over max_uncommitted_size                 */
+  QB_PSTAT_DROP_NO_LEADER = 5,      /* a follower with lead == 0                 */
+  QB_PSTAT_DROP_FORWARDING = 6,     /* a follower under disable_proposal_forwarding */
+  QB_PSTAT_DROP_CANDIDATE = 7,      /* a (pre-)candidate                         */
+  QB_PSTAT_FORWARDED = 8,
+  QB_PSTAT_CC_ACCEPTED = 9,         /* pending_conf_index set                    */
+  QB_PSTAT_CC_REFUSED = 10,
+  QB_PSTAT_MSG_APP = 11,
+  QB_PSTAT_MSG_SNAP = 12,
+  QB_PSTAT_COMMITS = 13,
+  QB_PSTAT_LEADER_ENTRIES = 14,
+  QB_PSTAT_LOG_RUNS = 15,
+  QB_PSTAT_EMPTY = 16,              /* n_ents == 0 at a leader                   */
+  QB_PSTAT_IGNORED_ROLE = 17,       /* QB_PROP_LEADER_ENTRY at a non-leader      */
+  QB_PSTAT_BAD_ACTION = 18,
+  QB_PSTAT_COUNT = 19
+};
+
+/* The arrays are those of qb_leader_groups, qb_follower_groups and
+ * qb_follower_log (same layouts: a caller passes the same buffers) plus
+ * applied, uncommitted_size and pending_conf_index. */
+typedef struct qb_propose_groups {
+  uint64_t G;
+  uint32_t inflight_cap;                /* 1..4096                              */
+  uint32_t disable_proposal_forwarding; /* 0 / 1                                */
+  uint64_t max_uncommitted_size;        /* 0 = no limit                         */
+  const uint32_t* off;          /* [G+1] */
+  const uint32_t* cfg;          /* [G] */
+  const uint8_t* role;          /* [G] QB_ROLE_* */
+  const uint64_t* term;         /* [G] */
+  const uint64_t* lead;         /* [G] */
+  const uint64_t* first_index;  /* [G] */
+  const uint64_t* snap_index;   /* [G] */
+  const uint64_t* snap_term;    /* [G] */
+  const uint64_t* max_ents;     /* [G] */
+  const uint64_t* applied;      /* [G] raftLog.applied */
+  uint32_t* meta;               /* [G] in/out: only bits 16-19 may change */
+  uint64_t* committed;          /* [G] in/out */
+  uint64_t* last_index;         /* [G] in/out */
+  uint64_t* last_term;          /* [G] in/out */
+  uint64_t* run_start;          /* [QB_LEADER_MAX_RUNS * G] in/out, run-major */
+  uint64_t* run_term;           /* same layout */
+  uint64_t* uncommitted_size;   /* [G] in/out: raft.uncommittedSize */
+  uint64_t* pending_conf_index; /* [G] in/out: raft.pendingConfIndex */
+  /* per slot, S = off[G] (in/out) */
+  uint64_t* match;
+  uint64_t* next;
+  uint64_t* pending_snapshot;
+  uint8_t* pstate;
+  uint32_t* infl_pos;
+  uint64_t* infl_buf;           /* [S * inflight_cap] */
+} qb_propose_groups;
+
+typedef struct qb_propose_in {  /* all [G] */
+  const uint8_t* action;      /* QB_PROP_* */
+  const uint32_t* n_ents;     /* len(m.Entries) */
+  const uint64_t* payload;    /* sum of PayloadSize over the entries */
+  const uint32_t* cc_at;      /* with QB_PROP_CONF_CHANGE */
+  const uint64_t* cc_payload; /* with QB_PROP_CONF_CHANGE */
+} qb_propose_in;
+
+typedef struct qb_propose_out {
+  uint8_t* pflags;        /* [G] QB_PFLAG_*, written for every group */
+  uint8_t* msg_type;      /* [S] written for every slot of a group with QB_PFLAG_BCAST
+                             and for no other slot */
+  uint64_t* msg_index;    /* [S] written only where msg_type != 0 */
+  uint64_t* msg_log_term; /* [S] same */
+  uint64_t* msg_n;        /* [S] same: entries of the MsgApp (0 for a MsgSnap) */
+} qb_propose_out;
+
+/* stats: QB_PSTAT_COUNT device uint64 (accumulated).  G == 0 is QB_OK and
+ * writes nothing; every pointer is required.  No workspace and no allocation
+ * inside the call (it can be graph-captured); nothing outside the caller's
+ * arrays is read or written. */
+int qb_dev_leader_propose(const qb_propose_groups* pg, const qb_propose_in* in,
+                          const qb_propose_out* out, uint64_t* stats, void* stream);
 
 /* ----------------------------------------------------------------------- */
 /* Wire ingest                                       */

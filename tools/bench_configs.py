@@ -1537,6 +1537,215 @@ def campaign_config(G, reps, *, reporter=None):
     assert ok, "campaign parity failed"
 
 
+def propose_config(G, reps, *, reporter=None):
+    """The batched proposal (qb_dev_leader_propose): G five-voter leader groups
+    of the synth_streaming table (own slot 0, the leader's term on top of the
+    log, rings of 4, 64 entries per MsgApp).  Sample (a): the steady proposal —
+    64 entries per group, every peer replicating with an empty ring at
+    next = last + 1: four MsgApp of 64 entries, OptimisticUpdate and
+    Inflights.Add per peer, no run table touched.  Sample (b): every peer
+    probing and unpaused: four MsgApp, ProbeSent set.  One HIP event pair per
+    call, median over the samples after warm-up; last_index, the own match,
+    next, pstate, infl_pos and uncommitted_size are restored between samples
+    outside the timed call.  Parity: one more call at the same size with seeded
+    roles, actions, entry counts, conf changes, sizes and peer Progress, every
+    1024th group against tests/propose_ref.py."""
+    reporter = reporter or report
+    import ctypes as C
+    import importlib
+    import time
+    from etcd_amd import _lib
+    from etcd_amd.quorum import propose as qp, tick as qt
+    from etcd_amd.quorum.leader import MAX_RUNS, _to_np, synth_streaming
+    from tests import propose_pack as P, propose_ref as R
+    qc = importlib.import_module("etcd_amd.quorum.campaign")
+    n, W, D, NE = 5, 4, 64, 64
+    lg, _ = synth_streaming(G, W=W, D=D, n=n, device=dev)
+    S = lg.S
+    z32 = lambda: torch.zeros(G, dtype=torch.int32, device=dev)  # noqa: E731
+    z64 = lambda: torch.zeros(G, dtype=torch.int64, device=dev)  # noqa: E731
+    state = qt.TickState(torch.full((G,), qt.ROLE_LEADER | qt.ROLE_PROMOTABLE, dtype=torch.uint8,
+                                    device=dev), z32(), z32(), z32())
+    lg.t["meta"].fill_(0xFF00 | (1 << 16))  # own slot 0, no transferee, one term run
+    es = qc.ElectionState.for_table(lg, state, np.arange(1, G + 1, dtype=np.uint64),
+                                    np.zeros(G, np.uint64), np.arange(1, G + 1, dtype=np.uint64),
+                                    np.full(G, 7, np.uint64), 10, True, True)
+    ps = qp.ProposeState(z64(), z64(), z64())
+    own = torch.arange(S, device=dev) % n == 0
+    lg.t["match"] = torch.where(own, lg.t["next"] - 1, lg.t["match"])
+    lg.t["infl_pos"].zero_()
+    ib = qp.ProposeInbox(torch.zeros(G, dtype=torch.uint8, device=dev),
+                         torch.full((G,), NE, dtype=torch.int32, device=dev),
+                         torch.full((G,), 8 * NE, dtype=torch.int64, device=dev), z32(), z64())
+    LIMIT = 1 << 30
+    out = qp.leader_propose(lg, es, ps, ib, max_uncommitted_size=LIMIT)  # (the mirror's checks, once)
+    sp = torch.cuda.current_stream(dev).cuda_stream
+    ft = es.follower.t
+    ptr = {k: lg.t[k].data_ptr() for k in ("off", "cfg", "first_index", "snap_index", "snap_term",
+                                           "max_ents", "meta", "run_start", "run_term", "match",
+                                           "next", "pending_snapshot", "pstate", "infl_pos",
+                                           "infl_buf")}
+    ptr.update({k: ft[k].data_ptr() for k in ("term", "lead", "committed", "last_index",
+                                              "last_term")})
+    pg = qp.ProposeGroupsC(G=G, inflight_cap=W, disable_proposal_forwarding=0,
+                           max_uncommitted_size=LIMIT, role=state.role.data_ptr(),
+                           applied=ps.applied.data_ptr(),
+                           uncommitted_size=ps.uncommitted_size.data_ptr(),
+                           pending_conf_index=ps.pending_conf_index.data_ptr(), **ptr)
+    pin = qp.ProposeInC(action=ib.action.data_ptr(), n_ents=ib.n_ents.data_ptr(),
+                        payload=ib.payload.data_ptr(), cc_at=ib.cc_at.data_ptr(),
+                        cc_payload=ib.cc_payload.data_ptr())
+    pout = qp.ProposeOutC(pflags=out.pflags.data_ptr(), msg_type=out.msg_type.data_ptr(),
+                          msg_index=out.msg_index.data_ptr(),
+                          msg_log_term=out.msg_log_term.data_ptr(), msg_n=out.msg_n.data_ptr())
+    fn = _lib.fn("qb_dev_leader_propose")
+    args = (C.byref(pg), C.byref(pin), C.byref(pout), out.stats.data_ptr(), sp)
+
+    def call():
+        _lib.check(fn(*args), "qb_dev_leader_propose")
+    keep = {k: lg.t[k].clone() for k in ("match", "next", "last_index")}
+    PR_REPL, PR_PROBE = 1 | 8, 0 | 8   # RecentActive set
+
+    def timed(peer_state):
+        pstate0 = torch.where(own, torch.full_like(lg.t["pstate"], PR_REPL),
+                              torch.full_like(lg.t["pstate"], peer_state))
+
+        def restore():
+            for k, v in keep.items():
+                lg.t[k].copy_(v)
+            lg.t["pstate"].copy_(pstate0)
+            lg.t["infl_pos"].zero_()
+            ps.uncommitted_size.zero_()
+            ib.action.fill_(qp.PROP_ENTRIES)
+
+        def sample(ev):
+            restore()
+            torch.cuda.synchronize()
+            ev.record(ev.ev[0], sp)
+            call()
+            ev.record(ev.ev[1], sp)
+            torch.cuda.synchronize()
+            return ev.elapsed_ms(0, 1) / 1e3
+        ev = HipEvents(2)
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < 0.3:  # warm-up: clocks settle (time_region)
+            sample(ev)
+        out.stats.zero_()
+        per = [sample(ev) for _ in range(reps)]
+        ev.close()
+        return float(np.median(per)), out.stats_dict()
+    t_repl, st = timed(PR_REPL)
+    assert st["proposals"] == reps * G and st["entries"] == reps * G * NE, st
+    assert st["msg_app"] == reps * G * (n - 1) and st["commits"] == 0 and st["drop_size"] == 0, st
+    assert bool((lg.t["infl_pos"].view(G, n)[:, 1:] == 1 << 16).all())   # one MsgApp in every ring
+    t_probe, st = timed(PR_PROBE)
+    assert st["proposals"] == reps * G and st["msg_app"] == reps * G * (n - 1), st
+    assert bool((lg.t["pstate"].view(G, n)[:, 1:] == (PR_PROBE | 4)).all())  # ProbeSent
+    # per group, read by every proposing group: action 1, role 1, meta 4, cfg 4,
+    # off 4, term / last_index / last_term / committed 32, n_ents 4, payload 8,
+    # uncommitted_size 8, max_ents 8, first_index 8 = 82 B; written: last_index 8,
+    # uncommitted_size 8, pflags 1 = 17 B.  Every slot's match is read for
+    # maybeCommit (8 B); the own slot: next 8 read and written, pstate 1 read,
+    # match 8 written, msg_type 1 = 26 B.  A peer, read: next 8, pstate 1,
+    # infl_pos 4; written: msg_type 1, msg_index / msg_log_term / msg_n 24, and
+    # (a) next 8, infl_pos 4, infl_buf 8 = 58 B, (b) pstate 1 = 39 B.
+    repl_b = 82 + 17 + n * 8 + 26 + (n - 1) * 58
+    probe_b = 82 + 17 + n * 8 + 26 + (n - 1) * 39
+    extra = {"unit": "groups/s", "samples": reps, "entries_per_proposal": NE, "inflight_cap": W,
+             "replicate_us": t_repl * 1e6, "replicate_bytes_per_group": repl_b,
+             "replicate_TBs": G * repl_b / t_repl / 1e12,
+             "replicate_frac": G * repl_b / t_repl / 1e9 / HBM_PEAK_GBS,
+             "probe_us": t_probe * 1e6, "probe_bytes_per_group": probe_b,
+             "probe_TBs": G * probe_b / t_probe / 1e12,
+             "probe_frac": G * probe_b / t_probe / 1e9 / HBM_PEAK_GBS,
+             "timing": "one HIP event pair per call, median over the samples; per_launch_us = "
+                       "sample (a), every peer replicating"}
+    # parity at this size
+    for k, v in keep.items():
+        lg.t[k].copy_(v)
+    gen = torch.Generator(device=dev).manual_seed(0x9805E)
+    rnd = lambda hi, k: torch.randint(0, hi, (k,), generator=gen, device=dev)  # noqa: E731
+    state.role.copy_((torch.where(rnd(4, G) == 0, rnd(4, G), torch.full((G,), 2, device=dev))
+                      | (1 << 7)).to(torch.uint8))
+    ft["lead"].copy_(rnd(2, G) * 9)
+    ft["term"].copy_(ft["term"] + torch.where(rnd(8, G) == 0, 1, 0))    # some need a new run
+    lg.t["meta"].copy_((lg.t["meta"] & ~0xFFFF | rnd(n + 1, G)
+                        | torch.where(rnd(16, G) == 0, rnd(n, G), torch.full((G,), 0xFF, device=dev))
+                        << 8).to(torch.int32))
+    gs = torch.arange(S, device=dev) // n
+    last = keep["last_index"][gs]
+    lg.t["next"].copy_(torch.where(own, keep["next"], last + 1 - rnd(200, S)))
+    lg.t["match"].copy_(torch.where(own, keep["match"], last - 200 + rnd(201, S)))
+    lg.t["pstate"].copy_(torch.where(own, torch.full((S,), PR_REPL, device=dev),
+                                     rnd(3, S) | rnd(4, S) << 2).to(torch.uint8))
+    lg.t["infl_pos"].copy_((rnd(W, S) | rnd(W + 1, S) << 16).to(torch.int32))
+    ps.applied.copy_(rnd(4, G))
+    ps.pending_conf_index.copy_(rnd(6, G))
+    ps.uncommitted_size.copy_(torch.where(rnd(2, G) == 0, 0, LIMIT - rnd(1024, G)))
+    ib.action.copy_((rnd(3, G) | torch.where(rnd(4, G) == 0, rnd(4, G) << 6, 0)).to(torch.uint8))
+    ib.n_ents.copy_(rnd(65, G).to(torch.int32))
+    ib.cc_at.copy_(rnd(70, G).to(torch.int32))
+    ib.cc_payload.copy_(rnd(300, G))
+    ib.payload.copy_(ib.cc_payload + rnd(700, G))
+    sub = np.arange(0, G, 1024)
+    slots = (sub[:, None] * n + np.arange(n)[None, :]).ravel()
+    rows = (np.arange(MAX_RUNS)[:, None] * G + sub[None, :]).ravel()
+    ring = (slots[:, None] * W + np.arange(W)[None, :]).ravel()
+
+    def gather():
+        a = {k: _to_np(lg.t[k], dt)[sub].copy() for k, dt in (
+            ("cfg", np.uint32), ("meta", np.uint32), ("term", np.uint64), ("committed", np.uint64),
+            ("first_index", np.uint64), ("last_index", np.uint64), ("snap_index", np.uint64),
+            ("snap_term", np.uint64), ("max_ents", np.uint64))}
+        a.update({k: _to_np(lg.t[k], np.uint64)[rows].copy() for k in ("run_start", "run_term")})
+        a.update({k: _to_np(lg.t[k], dt)[slots].copy() for k, dt in (
+            ("match", np.uint64), ("next", np.uint64), ("pending_snapshot", np.uint64),
+            ("pstate", np.uint8), ("infl_pos", np.uint32))})
+        a["infl_buf"] = _to_np(lg.t["infl_buf"], np.uint64)[ring].copy()
+        a["off"] = np.arange(len(sub) + 1, dtype=np.uint32) * n
+        a.update({k: np.zeros(0, dt) for k, dt in (("rq_ctx", np.uint64), ("rq_index", np.uint64),
+                                                   ("rq_meta", np.uint32))})
+        e = {k: v[sub].copy() for k, v in es.numpy().items()}
+        p = {k: v[sub].copy() for k, v in ps.numpy(G).items()}
+        return a, e, p
+    a0, e0, p0 = gather()
+    nodes = P.nodes_from_arrays(a0, e0, p0, W)
+    inp = {k: _to_np(getattr(ib, k), dt, G)[sub].copy() for k, dt in (
+        ("action", np.uint8), ("n_ents", np.uint32), ("payload", np.uint64), ("cc_at", np.uint32),
+        ("cc_payload", np.uint64))}
+    fill = P.FILL - (1 << 64)
+    out.msg_type.fill_(P.FILL8)
+    for t_ in (out.msg_index, out.msg_log_term, out.msg_n):
+        t_.fill_(fill)
+    out.stats.zero_()
+    call()
+    torch.cuda.synchronize()
+    msg = P.new_msg(len(slots))
+    pf, _, _ = P.ref_propose(nodes, inp, R.Config(max_uncommitted_size=LIMIT), a0["off"], msg)
+    want_a, want_e, want_p = P.pack_nodes(nodes, W)
+    a1, e1, p1 = gather()
+    keys = ("meta", "committed", "last_index", "run_start", "run_term", "match", "next",
+            "pending_snapshot", "pstate", "infl_pos", "infl_buf")
+    ok = (all(np.array_equal(a1[k], want_a[k]) for k in keys)
+          and all(np.array_equal(e1[k], want_e[k]) for k in want_e)
+          and all(np.array_equal(p1[k], want_p[k]) for k in want_p)
+          and np.array_equal(out.pflags.cpu().numpy()[sub], pf)
+          and all(np.array_equal(_to_np(getattr(out, k), msg[k].dtype, S)[slots], msg[k])
+                  for k in msg))
+    st = out.stats_dict()
+    ok = ok and all(st[k] > 0 for k in ("proposals", "leader_entries", "drop_size", "cc_accepted",
+                                        "cc_refused", "msg_app", "commits", "forwarded"))
+    extra["parity"] = bool(ok)
+    extra["parity_check"] = (f"tests/propose_ref.py over {len(sub)} groups (every 1024th) of the "
+                             f"{G} with seeded roles, own slots, terms, peer Progress, actions, "
+                             f"entry counts, conf changes and sizes: state, Progress, rings, run "
+                             f"tables, pflags and msg_* (untouched elements included); the call's "
+                             f"stats: {st}")
+    reporter("propose (64-entry MsgProp, appendEntry + bcastAppend; peers replicating)", G, t_repl,
+             G * repl_b, extra)
+    assert ok, "propose parity failed"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -1582,6 +1791,8 @@ def main():
         follower_log_config(1 << 22, a.reps)
     if "campaign" in which:
         campaign_config(1 << 22, a.reps)
+    if "propose" in which:
+        propose_config(1 << 22, a.reps)
     if "wire-tracker" in which:
         wire_tracker_config(1 << 24, a.reps)
     if "wire-tracker-fused" in which:  # development A/B: the one call alone
