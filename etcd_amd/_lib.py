@@ -89,6 +89,7 @@ SIGNATURES = {
     "qb_dev_follower_log_step": (_i32, [_p] * 11 + [C.c_size_t, _p]),
     "qb_dev_campaign": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p]),
     "qb_dev_leader_propose": (_i32, [_p, _p, _p, _p, _p]),
+    "qb_dev_leader_requests": (_i32, [_p, _p, _p, _p, _p]),
     "qb_dev_ingest_messages": (_i32, [_u64, _p, _u64, _p, _p, _u64, _p, _p, _p, _p, _p, _p, _p,
                                       _p, _p, _p, _p, _p]),
     "qb_wire_group_rows_bytes": (C.c_size_t, [_u64]),

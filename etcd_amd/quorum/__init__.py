@@ -24,6 +24,7 @@ from .campaign import CampaignResult, ElectionState, campaign
 from .follower import (FollowerAppInbox, FollowerGroups, FollowerInbox, FollowerLog,
                        FollowerLogResult, FollowerResult, follower_log_step, follower_step)
 from .propose import ProposeInbox, ProposeResult, ProposeState, leader_propose
+from .request import RequestInbox, RequestResult, leader_requests
 from .tick import TickResult, TickState, leader_tick
 
 MAX_UINT64 = INDEX_INF
@@ -180,6 +181,6 @@ def vote_results(configs: Sequence[JointConfig], votes: Sequence[Mapping[int, bo
 
 
 __all__ = ["AckedIndexer", "CampaignResult", "ElectionState", "FollowerAppInbox", "FollowerGroups", "FollowerInbox", "FollowerLog", "FollowerLogResult", "FollowerResult", "INDEX_INF",
-           "JointConfig", "MAX_UINT64", "MajorityConfig", "MapAckIndexer", "ProposeInbox", "ProposeResult", "ProposeState", "TickResult",
-           "TickState", "VoteLost", "VotePending", "VoteResult", "VoteWon", "batch", "campaign", "committed_indexes", "follower_log_step", "follower_step", "index_string", "leader_propose", "leader_tick",
+           "JointConfig", "MAX_UINT64", "MajorityConfig", "MapAckIndexer", "ProposeInbox", "ProposeResult", "ProposeState", "RequestInbox", "RequestResult", "TickResult",
+           "TickState", "VoteLost", "VotePending", "VoteResult", "VoteWon", "batch", "campaign", "committed_indexes", "follower_log_step", "follower_step", "index_string", "leader_propose", "leader_requests", "leader_tick",
            "vote_results"]

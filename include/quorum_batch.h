@@ -1315,6 +1315,211 @@ int qb_dev_leader_propose(const qb_propose_groups* pg, const qb_propose_in* in,
                           const qb_propose_out* out, uint64_t* stats, void* stream);
 
 /* ----------------------------------------------------------------------- */
+/* Requests: MsgReadIndex and MsgTransferLeader                            */
+/* ----------------------------------------------------------------------- */
+
+/* Step(MsgReadIndex) and Step(MsgTransferLeader) for G groups in one call
+ * (stepLeader raft.go:1078-1097 and 1339-1370, sendMsgReadIndexResponse
+ * raft.go:1827-1843, readOnly.addRequest / recvAck read_only.go:56-76,
+ * bcastHeartbeatWithCtx raft.go:495-541, stepFollower raft.go:1445-1464):
+ * the call that enqueues what qb_dev_leader_step later acknowledges and
+ * releases, and that sets the transferee whose catch-up qb_dev_leader_step
+ * answers with QB_MSG_TIMEOUT_NOW.  Dense, groups independent: per group up
+ * to max_reads read requests (the host concatenates a group's MsgReadIndex
+ * as it concatenates MsgProps) and at most one transfer request.
+ *
+ * ORDER.  Within a group the call applies the reads in k order, then the
+ * transfer.  The two kinds commute in every piece of state they touch (a
+ * read never changes Progress or the transferee; a transfer never changes
+ * committed, match or the read queue), so any interleaving of the same
+ * messages in the reference ends in the same state and the same outputs.
+ *
+ * READS.  Request k of group g is rd_ctx[k * G + g] (the 8-byte context) from
+ * rd_from[k * G + g]: the requesting slot, or 0xFF for a local request
+ * (From == None); a request from the own slot counts as local
+ * (responseToReadIndexReq, raft.go:1737-1752).  A forwarded MsgReadIndex
+ * carries no term (raft.go:410-416), so there is no term filter.
+ *   At a leader, request by request, a later one seeing what an earlier one
+ *   queued:
+ *   1. a context of 0 (this library's empty context): QB_RD_BAD, not applied.
+ *   2. rd_from neither 0xFF nor below the group's slot count: QB_RD_HOST,
+ *      not applied (rq_meta can only name a slot).
+ *   3. IsSingleton (exactly one voter in the incoming half, none in the
+ *      outgoing): answered at committed — QB_RD_READ_STATE for a local
+ *      request, QB_RD_RESP (a MsgReadIndexResp to the slot) for a remote
+ *      one; rd_index = committed.
+ *   4. !committedEntryInCurrentTerm (term(committed) through the run table
+ *      != term; term() is 0 outside [first_index - 1, last_index]):
+ *      QB_META_PENDING_READINDEX is set, QB_RD_POSTPONED; the host keeps the
+ *      message, as for QB_LFLAG_RELEASE_READS, and submits it again here.
+ *   5. QB_READ_ONLY_LEASE_BASED: answered at committed as in 3.
+ *   6. QB_READ_ONLY_SAFE: addRequest — a context already pending adds
+ *      nothing; a new one is written at the queue's end (rq_ctx = ctx,
+ *      rq_index = committed, rq_meta = from << 16) and the count in meta
+ *      bits 20-24 grows; recvAck(r.id) — the own slot's ack bit is set on
+ *      the entry, new or old (no bit for an own slot >= 16);
+ *      bcastHeartbeatWithCtx — QB_RD_BCAST (new entry) or QB_RD_BCAST_DUP,
+ *      QB_QFLAG_HEARTBEATS, and hb_commit[s] = min(match[s], committed[g])
+ *      for every slot of the group but the own one, voters and learners, as
+ *      the tick writes it.  The host forms one MsgHeartbeat per such slot and
+ *      per broadcasting request, with that request's context.  A new context
+ *      against a full queue (count == readq_cap, readq_cap 0 included):
+ *      QB_RD_QUEUE_FULL, nothing applied, the host submits it again; a
+ *      duplicate of a pending context behind a full queue still acks and
+ *      broadcasts.
+ *   At a follower (raft.go:1458-1464): lead != 0 is QB_RD_FORWARD (the host
+ *   sends the request to lead[g]), else QB_RD_DROPPED.  At a (pre-)candidate:
+ *   QB_RD_IGNORED (stepCandidate has no case for it).
+ *
+ * TRANSFER.  xf_from[g] is the transferee's slot (Message.From), 0xFF for no
+ * request; xf_term[g] is Message.Term, 0 for a local message (a forwarded
+ * MsgTransferLeader carries its sender's term).  In every role first Step's
+ * term filter: a non-zero term below the group's is ignored, one above it is
+ * the host's (QB_QFLAG_HOST: Step would becomeFollower) and nothing is
+ * applied.  Then at a leader, in the reference's order:
+ *   2. no Progress (slot >= the slot count) or a learner (in neither voter
+ *      mask): ignored.
+ *   3. a transfer is pending (meta bits 8-15 != 0xFF): to the same slot —
+ *      ignored; else aborted (transferee := 0xFF, QB_QFLAG_TRANSFER_ABORTED)
+ *      and the steps go on.
+ *   4. the transferee is the own slot: ignored (after 3: a transfer to self
+ *      still aborts a previous one).
+ *   5. election_elapsed := 0, transferee := slot (QB_QFLAG_TRANSFER_STARTED);
+ *      match[slot] == last_index sends QB_MSG_TIMEOUT_NOW, else sendAppend =
+ *      maybeSendAppend(slot, true) exactly as qb_dev_leader_propose sends
+ *      (paused rule, term(next - 1), min(max_ents, last - next + 1) entries,
+ *      the MsgSnap fallback with RecentActive and snap_index != 0 and
+ *      BecomeSnapshot, OptimisticUpdate + Inflights.Add in Replicate,
+ *      ProbeSent in Probe).  xf_type[g] = 0 / QB_MSG_TIMEOUT_NOW / QB_MSG_APP
+ *      / QB_MSG_SNAP; a MsgApp is {To: xf_from[g], Index: xf_index[g],
+ *      LogTerm: xf_log_term[g], Commit: committed[g], xf_n[g] entries}, a
+ *      MsgSnap carries the snapshot's index and term there.
+ * At a follower: lead != 0 is QB_QFLAG_FORWARD, else dropped.  At a
+ * (pre-)candidate: ignored.
+ *
+ * n_reads[g] > max_reads is read as max_reads and counted; a slot count above
+ * QB_MAX_SLOTS is read as QB_MAX_SLOTS, a run count of 0 as 1 and above 8 as
+ * 8, a request count above readq_cap as readq_cap.  Nothing outside the
+ * caller's arrays is read or written, whatever they hold. */
+#define QB_REQ_MAX_READS 16
+
+/* rd_status */
+#define QB_RD_READ_STATE 1  /* a ReadState{rd_index, ctx} for the local reader   */
+#define QB_RD_RESP 2        /* MsgReadIndexResp{To: rd_from, Index: rd_index, ctx} */
+#define QB_RD_BCAST 3       /* queued; heartbeats with the context               */
+#define QB_RD_BCAST_DUP 4   /* already pending; acked, heartbeats again          */
+#define QB_RD_POSTPONED 5   /* no commit in this term yet: the host keeps it     */
+#define QB_RD_FORWARD 6     /* a follower: the host sends it to lead[g]          */
+#define QB_RD_DROPPED 7     /* a follower without a leader                       */
+#define QB_RD_IGNORED 8     /* a (pre-)candidate                                 */
+#define QB_RD_QUEUE_FULL 9  /* not applied: submit again                         */
+#define QB_RD_HOST 10       /* rd_from names no slot: the host's                 */
+#define QB_RD_BAD 11        /* a context of 0                                    */
+
+#define QB_QFLAG_HEARTBEATS 0x01u        /* hb_commit of the group's peer slots written */
+#define QB_QFLAG_POSTPONED 0x02u         /* a read was postponed                 */
+#define QB_QFLAG_TRANSFER_STARTED 0x04u  /* transferee set, xf_type says what was sent */
+#define QB_QFLAG_TRANSFER_ABORTED 0x08u  /* the previous transfer was aborted    */
+#define QB_QFLAG_FORWARD 0x10u           /* a request goes to lead[g]            */
+#define QB_QFLAG_HOST 0x20u              /* a request is left to the host        */
+#define QB_QFLAG_BAD 0x40u               /* a zero context / n_reads > max_reads */
+
+enum {
+  QB_QSTAT_READ_STATES = 0,        /* QB_RD_READ_STATE                        */
+  QB_QSTAT_READ_RESPS = 1,         /* QB_RD_RESP                              */
+  QB_QSTAT_BCAST = 2,              /* QB_RD_BCAST                             */
+  QB_QSTAT_BCAST_DUP = 3,          /* QB_RD_BCAST_DUP                         */
+  QB_QSTAT_POSTPONED = 4,
+  QB_QSTAT_RD_FORWARD = 5,
+  QB_QSTAT_RD_DROPPED = 6,
+  QB_QSTAT_RD_IGNORED = 7,
+  QB_QSTAT_QUEUE_FULL = 8,
+  QB_QSTAT_RD_HOST = 9,
+  QB_QSTAT_BAD_CTX = 10,           /* QB_RD_BAD                               */
+  QB_QSTAT_BAD_COUNT = 11,         /* groups with n_reads > max_reads         */
+  QB_QSTAT_BCAST_GROUPS = 12,      /* groups with QB_QFLAG_HEARTBEATS         */
+  QB_QSTAT_XF_STARTED = 13,
+  QB_QSTAT_XF_TIMEOUT_NOW = 14,
+  QB_QSTAT_XF_MSG_APP = 15,
+  QB_QSTAT_XF_MSG_SNAP = 16,
+  QB_QSTAT_XF_ABORTED = 17,
+  QB_QSTAT_XF_IGN_TERM = 18,       /* a lower term                            */
+  QB_QSTAT_XF_IGN_NO_PROGRESS = 19,
+  QB_QSTAT_XF_IGN_LEARNER = 20,
+  QB_QSTAT_XF_IGN_SAME = 21,       /* already transferring to that slot       */
+  QB_QSTAT_XF_IGN_SELF = 22,
+  QB_QSTAT_XF_IGN_ROLE = 23,       /* a (pre-)candidate                       */
+  QB_QSTAT_XF_FORWARD = 24,
+  QB_QSTAT_XF_DROPPED = 25,        /* a follower without a leader             */
+  QB_QSTAT_XF_HOST = 26,           /* a higher term                           */
+  QB_QSTAT_COUNT = 27
+};
+
+/* The arrays are those of qb_leader_groups, qb_tick_groups,
+ * qb_follower_groups and qb_propose_groups (same layouts: a caller passes
+ * the same buffers). */
+typedef struct qb_request_groups {
+  uint64_t G;
+  uint32_t inflight_cap;        /* 1..4096                                  */
+  uint32_t readq_cap;           /* 0..QB_LEADER_MAX_READQ                   */
+  uint32_t read_only;           /* QB_READ_ONLY_SAFE / QB_READ_ONLY_LEASE_BASED */
+  uint32_t max_reads;           /* rows of rd_*: 1..QB_REQ_MAX_READS        */
+  const uint32_t* off;          /* [G+1] */
+  const uint32_t* cfg;          /* [G] */
+  uint32_t* meta;               /* [G] in/out: bits 8-15, 20-24 and 25 may change */
+  const uint8_t* role;          /* [G] QB_ROLE_* */
+  const uint64_t* term;         /* [G] */
+  const uint64_t* lead;         /* [G] */
+  const uint64_t* committed;    /* [G] */
+  const uint64_t* first_index;  /* [G] */
+  const uint64_t* last_index;   /* [G] */
+  const uint64_t* last_term;    /* [G] */
+  const uint64_t* snap_index;   /* [G] */
+  const uint64_t* snap_term;    /* [G] */
+  const uint64_t* max_ents;     /* [G] */
+  const uint64_t* run_start;    /* [QB_LEADER_MAX_RUNS * G] run-major */
+  const uint64_t* run_term;     /* same layout */
+  uint32_t* election_elapsed;   /* [G] in/out */
+  /* per slot, S = off[G] */
+  const uint64_t* match;
+  uint64_t* next;               /* in/out */
+  uint64_t* pending_snapshot;   /* in/out */
+  uint8_t* pstate;              /* in/out */
+  uint32_t* infl_pos;           /* in/out */
+  uint64_t* infl_buf;           /* [S * inflight_cap] in/out */
+  /* the pending ReadIndex queue, [G * readq_cap] (in/out); NULL iff readq_cap == 0 */
+  uint64_t* rq_ctx;
+  uint64_t* rq_index;
+  uint32_t* rq_meta;
+} qb_request_groups;
+
+typedef struct qb_request_in {
+  const uint8_t* n_reads;   /* [G] <= max_reads */
+  const uint64_t* rd_ctx;   /* [max_reads * G] k-major, as qb_leader_outbox::read_states */
+  const uint8_t* rd_from;   /* [max_reads * G] k-major: slot, 0xFF = local */
+  const uint8_t* xf_from;   /* [G] transferee slot, 0xFF = no request */
+  const uint64_t* xf_term;  /* [G] Message.Term, 0 = local; NULL: all local */
+} qb_request_in;
+
+typedef struct qb_request_out {
+  uint8_t* rd_status;     /* [max_reads * G] QB_RD_*, written only for k < n_reads[g] */
+  uint64_t* rd_index;     /* [max_reads * G] written where rd_status is QB_RD_READ_STATE / QB_RD_RESP */
+  uint64_t* hb_commit;    /* [S] written only in the peer slots of groups with QB_QFLAG_HEARTBEATS */
+  uint8_t* xf_type;       /* [G] written for every group: 0 / QB_MSG_TIMEOUT_NOW / QB_MSG_APP / QB_MSG_SNAP */
+  uint64_t* xf_index;     /* [G] written where xf_type is QB_MSG_APP / QB_MSG_SNAP */
+  uint64_t* xf_log_term;  /* [G] same */
+  uint64_t* xf_n;         /* [G] same: entries of the MsgApp (0 for a MsgSnap) */
+  uint8_t* qflags;        /* [G] QB_QFLAG_*, written for every group */
+} qb_request_out;
+
+/* stats: QB_QSTAT_COUNT device uint64 (accumulated).  G == 0 is QB_OK and
+ * writes nothing; every pointer but xf_term (and the queue's with readq_cap
+ * 0) is required.  No workspace and no allocation inside the call (it can be
+ * graph-captured). */
+int qb_dev_leader_requests(const qb_request_groups* rg, const qb_request_in* in,
+                           const qb_request_out* out, uint64_t* stats, void* stream);
+
+/* ----------------------------------------------------------------------- */
 /* Wire ingest                                       */
 /* ----------------------------------------------------------------------- */
 

@@ -1746,6 +1746,211 @@ def propose_config(G, reps, *, reporter=None):
     assert ok, "propose parity failed"
 
 
+def requests_config(G, reps, *, reporter=None):
+    """The batched requests (qb_dev_leader_requests): G five-voter leader groups
+    of the synth_streaming table (own slot 0, one term run, committed inside
+    it) with a read queue of 4 rows.  Sample (a): one local ReadOnlySafe read
+    per group against an empty queue — the row is written, the count grows and
+    four hb_commit go out.  Sample (b): the same plus a transfer to a
+    caught-up peer (slot 1): transferee set, election_elapsed zeroed,
+    MsgTimeoutNow.  One HIP event pair per call, median over the samples after
+    warm-up; meta (queue count, transferee), election_elapsed and the Progress
+    columns are put back between samples outside the timed call.  Parity: one
+    more call at the same size with seeded roles, own slots, terms, queues,
+    peer Progress and requests, every 1024th group against
+    tests/request_ref.py."""
+    reporter = reporter or report
+    import ctypes as C
+    import importlib
+    import time
+    from etcd_amd import _lib
+    from etcd_amd.quorum import request as qr, tick as qt
+    from etcd_amd.quorum.leader import MAX_RUNS, _to_np, synth_streaming
+    from tests import request_pack as Q, request_ref as R
+    qc = importlib.import_module("etcd_amd.quorum.campaign")
+    n, W, D, QC, MR = 5, 4, 64, 4, 2
+    lg, _ = synth_streaming(G, W=W, D=D, n=n, device=dev)
+    S = lg.S
+    lg.readq_cap = QC
+    lg.t["rq_ctx"] = torch.zeros(G * QC, dtype=torch.int64, device=dev)
+    lg.t["rq_index"] = torch.zeros(G * QC, dtype=torch.int64, device=dev)
+    lg.t["rq_meta"] = torch.zeros(G * QC, dtype=torch.int32, device=dev)
+    z32 = lambda: torch.zeros(G, dtype=torch.int32, device=dev)  # noqa: E731
+    state = qt.TickState(torch.full((G,), qt.ROLE_LEADER | qt.ROLE_PROMOTABLE, dtype=torch.uint8,
+                                    device=dev), z32(), z32(), z32())
+    lg.t["meta"].fill_(0xFF00 | (1 << 16))  # own slot 0, no transferee, one term run, queue empty
+    es = qc.ElectionState.for_table(lg, state, np.arange(1, G + 1, dtype=np.uint64),
+                                    np.zeros(G, np.uint64), np.arange(1, G + 1, dtype=np.uint64),
+                                    np.full(G, 7, np.uint64), 10, True, True)
+    slot = torch.arange(S, device=dev) % n
+    own = slot == 0
+    gs = torch.arange(S, device=dev) // n
+    last = lg.t["last_index"][gs]
+    lg.t["match"] = torch.where(slot <= 1, last, lg.t["match"])   # slot 1 is caught up
+    ib = qr.RequestInbox(MR, torch.ones(G, dtype=torch.uint8, device=dev),
+                         torch.arange(1, MR * G + 1, dtype=torch.int64, device=dev),
+                         torch.full((MR * G,), 0xFF, dtype=torch.uint8, device=dev),
+                         torch.full((G,), 0xFF, dtype=torch.uint8, device=dev),
+                         torch.zeros(G, dtype=torch.int64, device=dev))
+    out = qr.new_result(G, S, MR, dev)
+    rg, rin, rout = qr.request_structs(lg, es, ib, out)  # (the mirror's checks, once)
+    sp = torch.cuda.current_stream(dev).cuda_stream
+    fn = _lib.fn("qb_dev_leader_requests")
+    args = (C.byref(rg), C.byref(rin), C.byref(rout), out.stats.data_ptr(), sp)
+
+    def call():
+        _lib.check(fn(*args), "qb_dev_leader_requests")
+    keys = ("meta", "match", "next", "pending_snapshot", "pstate", "infl_pos")
+    keep = {k: lg.t[k].clone() for k in keys}
+
+    def timed(xf):
+        ib.xf_from.fill_(xf)
+
+        def restore():
+            for k, v in keep.items():
+                lg.t[k].copy_(v)
+            state.election_elapsed.fill_(3)
+
+        def sample(ev):
+            restore()
+            torch.cuda.synchronize()
+            ev.record(ev.ev[0], sp)
+            call()
+            ev.record(ev.ev[1], sp)
+            torch.cuda.synchronize()
+            return ev.elapsed_ms(0, 1) / 1e3
+        ev = HipEvents(2)
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < 0.3:  # warm-up: clocks settle (time_region)
+            sample(ev)
+        out.stats.zero_()
+        per = [sample(ev) for _ in range(reps)]
+        ev.close()
+        return float(np.median(per)), out.stats_dict()
+    t_read, st = timed(0xFF)
+    assert st["bcast"] == reps * G and st["bcast_groups"] == reps * G and st["xf_started"] == 0, st
+    assert bool(((lg.t["meta"] >> 20) & 0x1F == 1).all())
+    assert bool((out.hb_commit.view(G, n)[:, 2:] == lg.t["committed"][:, None]).all())
+    t_both, st = timed(1)
+    assert st["bcast"] == reps * G and st["xf_timeout_now"] == reps * G, st
+    assert bool((state.election_elapsed == 0).all()) and bool(((lg.t["meta"] >> 8) & 0xFF == 1).all())
+    # per group, sample (a).  Read: n_reads 1, xf_from 1, role 1, meta 4, cfg 4,
+    # off 4, term / lead / committed / first_index / last_index / last_term 48,
+    # rd_ctx 8, rd_from 1 = 72 B; written: the queue row 8 + 8 + 4, meta 4,
+    # rd_status 1, qflags 1, xf_type 1 = 27 B; per peer: match 8 read, hb_commit
+    # 8 written = 16 B.  Sample (b) adds xf_term 8 and the transferee's match 8
+    # read, election_elapsed 4 written.
+    read_b = 72 + 27 + (n - 1) * 16
+    both_b = read_b + 20
+    extra = {"unit": "groups/s", "samples": reps, "readq_cap": QC, "max_reads": MR,
+             "read_us": t_read * 1e6, "read_bytes_per_group": read_b,
+             "read_TBs": G * read_b / t_read / 1e12,
+             "read_frac": G * read_b / t_read / 1e9 / HBM_PEAK_GBS,
+             "read_transfer_us": t_both * 1e6, "read_transfer_bytes_per_group": both_b,
+             "read_transfer_TBs": G * both_b / t_both / 1e12,
+             "read_transfer_frac": G * both_b / t_both / 1e9 / HBM_PEAK_GBS,
+             "timing": "one HIP event pair per call, median over the samples; per_launch_us = "
+                       "sample (a), one local safe read per group"}
+    # parity at this size
+    for k, v in keep.items():
+        lg.t[k].copy_(v)
+    gen = torch.Generator(device=dev).manual_seed(0x4EAD5)
+    rnd = lambda hi, k: torch.randint(0, hi, (k,), generator=gen, device=dev)  # noqa: E731
+    ft = es.follower.t
+    state.role.copy_((torch.where(rnd(4, G) == 0, rnd(4, G), torch.full((G,), 2, device=dev))
+                      | (1 << 7)).to(torch.uint8))
+    state.election_elapsed.copy_(rnd(9, G).to(torch.int32))
+    ft["lead"].copy_(rnd(2, G) * 9)
+    ft["term"].copy_(ft["term"] + torch.where(rnd(8, G) == 0, 1, 0))    # some have nothing committed
+    one = torch.ones(G, dtype=torch.int64, device=dev)
+    lg.t["cfg"].copy_(torch.where(rnd(16, G) == 0, one << rnd(n, G),    # singletons, learners
+                                  torch.where(rnd(8, G) == 0, 0b01111, 0b11111)).to(torch.int32))
+    nq = rnd(QC + 1, G)
+    lg.t["meta"].copy_((rnd(n + 1, G) | (1 << 16) | nq << 20 | rnd(2, G) << 25
+                        | torch.where(rnd(8, G) == 0, rnd(n, G), torch.full((G,), 0xFF, device=dev))
+                        << 8).to(torch.int32))
+    k_ = torch.arange(G * QC, device=dev) % QC
+    livek = k_ < nq.repeat_interleave(QC)
+    fill = Q.FILL - (1 << 64)
+    lg.t["rq_ctx"].copy_(torch.where(livek, 100 + k_, fill))
+    lg.t["rq_index"].copy_(torch.where(livek, rnd(1000, G * QC), fill))
+    lg.t["rq_meta"].copy_(torch.where(livek, rnd(1 << n, G * QC) | (rnd(2, G * QC) * 0xFF) << 16,
+                                      Q.FILL32 - (1 << 32)).to(torch.int32))
+    lg.t["next"].copy_(torch.where(own, keep["next"],
+                                   torch.where(rnd(16, S) == 0, lg.t["first_index"][gs] - 5,
+                                               last + 1 - rnd(200, S))))   # (some behind the log)
+    lg.t["match"].copy_(torch.where(own | (rnd(3, S) == 0), last, last - 200 + rnd(201, S)))
+    lg.t["pstate"].copy_(torch.where(own, torch.full((S,), 1 | 8, device=dev),
+                                     rnd(3, S) | rnd(4, S) << 2).to(torch.uint8))
+    lg.t["infl_pos"].copy_((rnd(W, S) | rnd(W + 1, S) << 16).to(torch.int32))
+    ib.n_reads.copy_(rnd(MR + 2, G).to(torch.uint8))
+    pool = torch.tensor([0, 100, 101, 102, 103, 200, 201, 202], device=dev)
+    ib.rd_ctx.copy_(pool[rnd(len(pool), MR * G)])
+    frm = torch.tensor([0xFF, 0xFF, 0, 1, n - 1, n, 0xFE], device=dev)
+    ib.rd_from.copy_(frm[rnd(len(frm), MR * G)].to(torch.uint8))
+    xfr = torch.tensor([0xFF, 0xFF, 0, 1, 2, 3, 4, n], device=dev)
+    ib.xf_from.copy_(xfr[rnd(len(xfr), G)].to(torch.uint8))
+    ib.xf_term.copy_(torch.where(rnd(2, G) == 0, 0, ft["term"] - 1 + rnd(3, G)))
+    sub = np.arange(0, G, 1024)
+    slots = (sub[:, None] * n + np.arange(n)[None, :]).ravel()
+    rows = (np.arange(MAX_RUNS)[:, None] * G + sub[None, :]).ravel()
+    ring = (slots[:, None] * W + np.arange(W)[None, :]).ravel()
+    qrows = (sub[:, None] * QC + np.arange(QC)[None, :]).ravel()
+    rdrows = (np.arange(MR)[:, None] * G + sub[None, :]).ravel()
+
+    def gather():
+        a = {k: _to_np(lg.t[k], dt)[sub].copy() for k, dt in (
+            ("cfg", np.uint32), ("meta", np.uint32), ("term", np.uint64), ("committed", np.uint64),
+            ("first_index", np.uint64), ("last_index", np.uint64), ("snap_index", np.uint64),
+            ("snap_term", np.uint64), ("max_ents", np.uint64))}
+        a.update({k: _to_np(lg.t[k], np.uint64)[rows].copy() for k in ("run_start", "run_term")})
+        a.update({k: _to_np(lg.t[k], dt)[slots].copy() for k, dt in (
+            ("match", np.uint64), ("next", np.uint64), ("pending_snapshot", np.uint64),
+            ("pstate", np.uint8), ("infl_pos", np.uint32))})
+        a["infl_buf"] = _to_np(lg.t["infl_buf"], np.uint64)[ring].copy()
+        a.update({k: _to_np(lg.t[k], dt)[qrows].copy() for k, dt in (
+            ("rq_ctx", np.uint64), ("rq_index", np.uint64), ("rq_meta", np.uint32))})
+        a["off"] = np.arange(len(sub) + 1, dtype=np.uint32) * n
+        e = {k: v[sub].copy() for k, v in es.numpy().items()}
+        return a, e
+    a0, e0 = gather()
+    nodes = Q.nodes_from_arrays(a0, e0, QC, W)
+    inp = {"n_reads": ib.n_reads.cpu().numpy()[sub].copy(),
+           "rd_ctx": _to_np(ib.rd_ctx, np.uint64)[rdrows].copy(),
+           "rd_from": ib.rd_from.cpu().numpy()[rdrows].copy(),
+           "xf_from": ib.xf_from.cpu().numpy()[sub].copy(),
+           "xf_term": _to_np(ib.xf_term, np.uint64)[sub].copy()}
+    for t_ in (out.rd_status, out.xf_type, out.qflags):
+        t_.fill_(Q.FILL8)
+    for t_ in (out.rd_index, out.hb_commit, out.xf_index, out.xf_log_term, out.xf_n):
+        t_.fill_(fill)
+    out.stats.zero_()
+    call()
+    torch.cuda.synchronize()
+    want = Q.new_out(len(sub), len(slots), MR)
+    Q.ref_requests(nodes, inp, R.Config(R.SAFE, QC, MR), a0["off"], want)
+    want_a, want_e = Q.pack_nodes(nodes, QC, W)
+    a1, e1 = gather()
+    where = {"rd_status": rdrows, "rd_index": rdrows, "hb_commit": slots}
+    ok = (all(np.array_equal(a1[k], want_a[k]) for k in (
+              "meta", "committed", "match", "next", "pending_snapshot", "pstate", "infl_pos",
+              "infl_buf", "rq_ctx", "rq_index", "rq_meta"))
+          and all(np.array_equal(e1[k], want_e[k]) for k in want_e)
+          and all(np.array_equal(_to_np(getattr(out, k), w.dtype)[where.get(k, sub)], w)
+                  for k, w in want.items()))
+    st = out.stats_dict()
+    ok = ok and all(v > 0 for v in st.values())   # every outcome was reached
+    extra["parity"] = bool(ok)
+    extra["parity_check"] = (f"tests/request_ref.py over {len(sub)} groups (every 1024th) of the "
+                             f"{G} with seeded roles, own slots, configs, terms, queues, peer "
+                             f"Progress, reads and transfers: meta, the queue rows, Progress, rings, "
+                             f"the election state, rd_* / hb_commit / xf_* / qflags (untouched "
+                             f"elements included); the call's stats: {st}")
+    reporter("requests (one safe MsgReadIndex per group: queue row + heartbeats)", G, t_read,
+             G * read_b, extra)
+    assert ok, "requests parity failed"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -1793,6 +1998,8 @@ def main():
         campaign_config(1 << 22, a.reps)
     if "propose" in which:
         propose_config(1 << 22, a.reps)
+    if "requests" in which:
+        requests_config(1 << 22, a.reps)
     if "wire-tracker" in which:
         wire_tracker_config(1 << 24, a.reps)
     if "wire-tracker-fused" in which:  # development A/B: the one call alone
