@@ -5,34 +5,20 @@
 // (raft.go:1399-1414, 724-758, 686-693), with reset (raft.go:590-619) over
 // every field the engine's arrays hold.
 //
-// One kernel, a streaming pass with no cross-group dependence, the shape of
-// k_tick.  A workgroup takes tiles of 256 consecutive groups, which own one
-// contiguous slot span [off[g0], off[g0 + 256]):
+// One kernel in the span-tile shape (qb_span_tile.h):
 //   P1  thread per group: the action byte first; a group with nothing to do
 //       writes its cflags / req_type bytes and is done.  An acting group
 //       requests all its group words at once (one HBM round trip), runs the
 //       transition in registers and writes the group words that changed.  A
-//       group whose transition runs reset names itself owner of its slots in
-//       LDS (one byte per slot of the span) and leaves its recipe there: own
-//       slot, last_index, leader / bcastAppend bits.
-//   P2  (only if a group of the tile resets) the workgroup strides the span
-//       and writes match, next, pending_snapshot, pstate and infl_pos of the
-//       owned slots as coalesced runs.  Reset reads no slot: the phase is
-//       write-only.  Slots of groups that do not reset touch nothing.
-// A tile in which nothing resets skips P2 and its barrier.  A span wider
-// than kSpanCap (a table with gaps) runs P2 with each thread looping over its
-// own group's slots in the global arrays.
-//
-// Statistics go through BlockTally; the grid is capped at the workgroups the
-// device holds at once, striding the tiles, as the tick does.
-#include "qb_common.h"
+//       group whose transition runs reset claims its slots and leaves its
+//       recipe in LDS: own slot, last_index, leader / bcastAppend bits.
+//   P2  (only if a group of the tile resets) match, next, pending_snapshot,
+//       pstate and infl_pos of the claimed slots are written.  Reset reads no
+//       slot: the phase is write-only.
+#include "qb_span_tile.h"
 
 namespace qb {
 namespace campaign {
-
-constexpr u32 kSpanCap = kBlock * QB_MAX_SLOTS;  // 4096: every well-formed tile
-constexpr unsigned kCampBlocks = 2048;
-constexpr u32 kUnroll = 4;  // slots per thread and trip
 
 // a resetting group's recipe (LDS, one byte per group of the tile)
 constexpr u8 kReset = 1;   // reset ran: the group's slots are rewritten
@@ -50,10 +36,8 @@ struct Args {
 };
 
 struct Tile {
-  u8 owner[kSpanCap];  // slot of the span -> thread (group) of the tile
+  SpanOwners slots;
   u64 last[kBlock];    // last_index at entry
-  u32 j0[kBlock];      // the group's first slot within the span
-  u8 ns[kBlock];       // its slot count (<= QB_MAX_SLOTS)
   u8 fl[kBlock];       // kReset | kLeader | kBcast; 0: the group's slots stay
   u8 own[kBlock];      // own slot, 0xFF = the node has no Progress
   u32 tally[QB_CSTAT_COUNT];
@@ -100,11 +84,10 @@ __global__ __launch_bounds__(kBlock) void k_campaign(Args A) {
   if (tid < QB_CSTAT_COUNT) T.tally[tid] = 0;
 
   for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const u64 g0 = tile * kBlock;
-    const u64 g = g0 + tid;
-    const u64 gend = g0 + kBlock < G ? g0 + kBlock : G;
+    SpanTile S(tile, G);
+    const u64 g = S.g0 + tid;
     const bool live = g < G;
-    const u32 sb = cg.off[g0], se = cg.off[gend];  // the tile's span (used in P2 only)
+    const u32 sb = cg.off[S.g0], se = cg.off[S.gend];  // the tile's span (used in P2 only)
 
     // ------------------------------------------------------------- P1 ---
     const u8 action = live ? A.action[g] : u8(0);
@@ -126,9 +109,9 @@ __global__ __launch_bounds__(kBlock) void k_campaign(Args A) {
       const u64 term0 = term_a[g], vote0 = vote_a[g], com0 = com_a[g];
       const u64 self = reinterpret_cast<const u64*>(cg.self_id)[g];
       last = reinterpret_cast<const u64*>(cg.last_index)[g];
-      ns = s1 > s0 ? (s1 - s0 < QB_MAX_SLOTS ? s1 - s0 : u32(QB_MAX_SLOTS)) : 0u;
-      const u32 min_ = cfg & 0xFFFFu, mout = cfg >> 16, voters = min_ | mout;
-      const u32 oslot = meta & 0xFFu;
+      ns = clamp_slots(s0, s1);
+      const u32 min_ = cfg_incoming(cfg), mout = cfg_outgoing(cfg), voters = min_ | mout;
+      const u32 oslot = meta_own_slot(meta);
       own = oslot < ns ? oslot : 0xFFu;
       const u32 ownbit = oslot < 16u ? 1u << oslot : 0u;
       const u32 state = role & 3u;
@@ -231,35 +214,26 @@ __global__ __launch_bounds__(kBlock) void k_campaign(Args A) {
     // ------------------------------------------------------------- P2 ---
     const bool fires = __syncthreads_or(fl != 0);  // (also: the previous tile's LDS is free)
     if (fires) {
-      const u32 span = se - sb;
-      const bool staged = se >= sb && span <= kSpanCap;  // workgroup-uniform
-      if (staged) {
-        const u32 j0 = s0 - sb;
-        // a staged group's slots lie inside the span for any monotone off; one
-        // that does not (a malformed table) resets no slot
-        if (fl && !(s0 >= sb && j0 <= span && ns <= span - j0)) ns = 0;
+      S.bound(sb, se);
+      if (S.staged) {
         if (fl) {
-          T.j0[tid] = j0;
-          T.ns[tid] = u8(ns);
+          ns = T.slots.claim(S, s0, ns);
           T.own[tid] = u8(own);
           T.last[tid] = last;
-          for (u32 k = 0; k < ns; ++k) T.owner[j0 + k] = u8(tid);
         }
         T.fl[tid] = fl;
         __syncthreads();
-        for (u32 jb = tid; jb < span; jb += kBlock * kUnroll) {
+        for (u32 jb = tid; jb < S.span; jb += kBlock * kSpanUnroll) {
 #pragma unroll
-          for (u32 u = 0; u < kUnroll; ++u) {
+          for (u32 u = 0; u < kSpanUnroll; ++u) {
             const u32 j = jb + u * kBlock;
-            if (j >= span) continue;
-            // a slot no resetting group owns holds a stale owner byte: the
-            // named owner's own range decides
-            const u32 t = T.owner[j];
+            if (j >= S.span) continue;
+            const SpanOwners::Slot o = T.slots.find(j);
+            const u32 t = o.t;
             const u8 f = T.fl[t];
-            const u32 k = j - T.j0[t];
-            if (!f || k >= T.ns[t]) continue;
-            const SlotImage s = slot_image(f, k == T.own[t], T.last[t]);
-            const u64 i = u64(sb) + j;
+            if (!f || !o.in) continue;
+            const SlotImage s = slot_image(f, o.k == T.own[t], T.last[t]);
+            const u64 i = u64(S.sb) + j;
             __builtin_nontemporal_store(s.match, match_a + i);
             __builtin_nontemporal_store(s.next, next_a + i);
             __builtin_nontemporal_store(0ull, psnap_a + i);
@@ -293,26 +267,7 @@ __global__ __launch_bounds__(kBlock) void k_campaign(Args A) {
   __syncthreads();  // T.tally zeroed; the last tile's LDS reads done
   tally.stage(T.tally);
   __syncthreads();
-  const int slot[QB_CSTAT_COUNT] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9};
-  BlockTally<QB_CSTAT_COUNT>::publish(T.tally, reinterpret_cast<u64*>(A.stats), slot);
-}
-
-// The grid's cap: the workgroups the device holds at once (occupancy x CUs);
-// kCampBlocks if the runtime will not say.  Asked once per process.
-inline unsigned resident_blocks() {
-  static const unsigned n = [] {
-    int dev = 0, per_cu = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_campaign, kBlock, 0) != hipSuccess ||
-        per_cu <= 0 || cus <= 0) {
-      (void)hipGetLastError();
-      return kCampBlocks;
-    }
-    const unsigned r = unsigned(per_cu) * unsigned(cus);
-    return r < kCampBlocks ? r : kCampBlocks;
-  }();
-  return n;
+  BlockTally<QB_CSTAT_COUNT>::publish(T.tally, reinterpret_cast<u64*>(A.stats));
 }
 
 }  // namespace campaign
@@ -336,9 +291,8 @@ extern "C" int qb_dev_campaign(const qb_campaign_groups* cg, const uint8_t* acti
              "req_term / req_mask / stats)");
   campaign::Args A{*cg, action, cflags, req_type, reinterpret_cast<u64*>(req_term), req_mask,
                    reinterpret_cast<u64*>(stats)};
-  const unsigned tiles = grid_for(cg->G), cap = campaign::resident_blocks();
-  hipLaunchKernelGGL(campaign::k_campaign, dim3(tiles < cap ? tiles : cap), dim3(kBlock), 0,
-                     as_stream(stream), A);
+  hipLaunchKernelGGL(campaign::k_campaign, dim3(stream_grid<campaign::k_campaign>(cg->G)),
+                     dim3(kBlock), 0, as_stream(stream), A);
   QB_CHECK_LAUNCH("k_campaign");
   return QB_OK;
 }

@@ -179,7 +179,25 @@ struct BlockTally {
   __device__ __forceinline__ static void publish(const u32* lds, u64* dst, const int (&slot)[K]) {
     if (threadIdx.x < K && lds[threadIdx.x]) atomicAdd(dst + slot[threadIdx.x], u64(lds[threadIdx.x]));
   }
+  // counter k at dst[k]
+  __device__ __forceinline__ static void publish(const u32* lds, u64* dst) {
+    if (threadIdx.x < K && lds[threadIdx.x]) atomicAdd(dst + threadIdx.x, u64(lds[threadIdx.x]));
+  }
 };
+
+// --------------------------------------------------- group words' fields ---
+// The meta word (quorum_batch.h, "Group meta word") and the cfg word's two
+// slot masks.
+__host__ __device__ __forceinline__ u32 meta_own_slot(u32 meta) { return meta & 0xFFu; }
+__host__ __device__ __forceinline__ u32 meta_transferee(u32 meta) { return (meta >> 8) & 0xFFu; }
+__host__ __device__ __forceinline__ u32 meta_readq_len(u32 meta) { return (meta >> 20) & 0x1Fu; }
+// the term runs, read as 1..QB_LEADER_MAX_RUNS
+__host__ __device__ __forceinline__ u32 meta_nruns(u32 meta) {
+  const u32 n = (meta >> 16) & 0xFu;
+  return n < 1u ? 1u : (n > QB_LEADER_MAX_RUNS ? u32(QB_LEADER_MAX_RUNS) : n);
+}
+__host__ __device__ __forceinline__ u32 cfg_incoming(u32 cfg) { return cfg & 0xFFFFu; }
+__host__ __device__ __forceinline__ u32 cfg_outgoing(u32 cfg) { return cfg >> 16; }
 
 
 // ------------------------------------------------------------- LDS-DMA ---

@@ -3,42 +3,28 @@
 // (qb_dev_leader_propose): raft.go:1019-1077, 621-642, 1761-1779, 432-522,
 // 745-756.  The one call that lets a leader's log grow on the device.
 //
-// One kernel, a streaming pass with no cross-group dependence, the shape of
-// k_campaign / k_tick.  A workgroup takes tiles of 256 consecutive groups,
-// which own one contiguous slot span [off[g0], off[g0 + 256]):
+// One kernel in the span-tile shape (qb_span_tile.h):
 //   P1  thread per group: the action byte first; a group with nothing to do
 //       writes its pflags byte and is done.  An acting group requests all its
 //       group words at once (one HBM round trip), decides the proposal (role,
 //       drops, the conf-change rule, the size limit, the run-table stop),
 //       appends, and in a second trip runs MaybeUpdate on its own slot and
-//       maybeCommit over its match values.  A group that broadcasts names
-//       itself owner of its slots in LDS (one byte per slot of the span) and
-//       leaves its recipe there: new last index, old last index and term,
-//       term, first index, entries per message, own slot.
-//   P2  (only if a group of the tile broadcasts) the workgroup strides the
-//       span with a thread per slot: next, pstate and infl_pos are read and
-//       written coalesced, maybeSendAppend runs per slot and the message
-//       columns are written.  Slots of groups that do not broadcast touch
-//       nothing.
+//       maybeCommit over its match values.  A group that broadcasts claims its
+//       slots and leaves its recipe in LDS: new last index, old last index and
+//       term, term, first index, entries per message, own slot.
+//   P2  (only if a group of the tile broadcasts) next, pstate and infl_pos are
+//       read, maybeSendAppend runs per slot and the message columns are
+//       written.
 // The term of next - 1 follows from the recipe wherever next - 1 is at or past
 // the old last index (old last: last_term; beyond it: the leader's term), so
 // the steady proposal reads and writes no run table; an older next - 1 walks
-// the group's runs (not its entries).  A span wider than kSpanCap (a table
-// with gaps) runs P2 with each thread looping over its own group's slots in
-// the global arrays.
+// the group's runs (not its entries).
 //
-// Progress and Inflights are restated here from qb_leader.hip (that
-// translation unit keeps them private to its staged step).  Statistics go
-// through BlockTally, the entry count through a 64-bit cell beside it; the
-// grid is capped at the workgroups the device holds at once.
-#include "qb_common.h"
+// The entry count goes through a 64-bit cell beside the BlockTally.
+#include "qb_span_tile.h"
 
 namespace qb {
 namespace propose {
-
-constexpr u32 kSpanCap = kBlock * QB_MAX_SLOTS;  // 4096: every well-formed tile
-constexpr unsigned kPropBlocks = 2048;
-constexpr u32 kUnroll = 4;  // slots per thread and trip
 
 struct Args {
   qb_propose_groups pg;
@@ -60,11 +46,9 @@ struct Recipe {
 };
 
 struct Tile {
-  u8 owner[kSpanCap];  // slot of the span -> thread (group) of the tile
+  SpanOwners slots;
   u64 last[kBlock], old[kBlock], term[kBlock], oldt[kBlock], ments[kBlock], first[kBlock];
-  u32 j0[kBlock];      // the group's first slot within the span
-  u8 ns[kBlock];       // its slot count (<= QB_MAX_SLOTS)
-  u8 fl[kBlock];       // non-zero: the group broadcasts
+  u8 fl[kBlock];      // non-zero: the group broadcasts
   u8 own[kBlock];      // own slot
   u8 nruns[kBlock];
   u32 tally[QB_PSTAT_COUNT];
@@ -77,70 +61,17 @@ __device__ __forceinline__ u64 term_at(const Args& A, const Recipe& r, u64 i) {
   if (i < r.first - 1 || i > r.last) return 0;
   if (i > r.old) return r.term;
   if (i == r.old) return r.oldt;
-  const u64 G = A.pg.G;
-  const u64* rs = reinterpret_cast<const u64*>(A.pg.run_start) + r.g;  // run q at rs[q * G]
-  const u64* rt = reinterpret_cast<const u64*>(A.pg.run_term) + r.g;
-  u64 t = 0;
-  for (u32 q = 0; q < r.nruns; ++q)
-    if (rs[q * G] <= i) t = rt[q * G];
-  return t;
+  return walk_runs(A.pg.run_start, A.pg.run_term, A.pg.G, r.g, i, r.nruns);
 }
 
-// maybeSendAppend(to, true) (raft.go:432-492) on slot i, whose next / pstate /
-// infl_pos the caller has read.  Returns the message type (0: none).
+// maybeSendAppend on slot i of r's group, the message to the slot's columns.
 __device__ __forceinline__ u32 send_slot(const Args& A, const Recipe& r, u64 i, u64 nx, u8 st,
                                          u32 ipos) {
-  const qb_propose_groups& pg = A.pg;
-  const u32 K = pg.inflight_cap;
-  const u32 state = st & 3u;
-  // IsPaused (progress.go:193-212)
-  if (state == QB_PR_PROBE ? (st & QB_PR_PROBE_SENT) != 0
-                           : (state == QB_PR_REPLICATE ? (ipos >> 16) == K : true))
-    return 0;
-  const u64 lt = term_at(A, r, nx - 1);
-  u64 n = 0;
-  bool compacted = false;
-  if (nx <= r.last) {
-    if (nx < r.first) compacted = true;  // ErrCompacted
-    else {
-      const u64 avail = r.last - nx + 1;
-      n = avail < r.ments ? avail : r.ments;
-    }
-  }
-  u64* __restrict__ mi = reinterpret_cast<u64*>(A.out.msg_index);
-  u64* __restrict__ ml = reinterpret_cast<u64*>(A.out.msg_log_term);
-  u64* __restrict__ mn = reinterpret_cast<u64*>(A.out.msg_n);
-  if (compacted) {
-    if (!(st & QB_PR_RECENT_ACTIVE)) return 0;
-    const u64 snapi = reinterpret_cast<const u64*>(pg.snap_index)[r.g];
-    if (snapi == 0) return 0;  // ErrSnapshotTemporarilyUnavailable
-    mi[i] = snapi;
-    ml[i] = reinterpret_cast<const u64*>(pg.snap_term)[r.g];
-    mn[i] = 0;
-    // BecomeSnapshot (progress.go:139-144)
-    pg.pstate[i] = u8((st & QB_PR_RECENT_ACTIVE) | QB_PR_SNAPSHOT);
-    reinterpret_cast<u64*>(pg.pending_snapshot)[i] = snapi;
-    pg.infl_pos[i] = 0;
-    return QB_MSG_SNAP;
-  }
-  mi[i] = nx - 1;
-  ml[i] = lt;
-  mn[i] = n;
-  if (n != 0) {
-    if (state == QB_PR_REPLICATE) {
-      // OptimisticUpdate (progress.go:159-161), Inflights.Add (inflights.go:55-70)
-      const u64 last = nx + n - 1;
-      reinterpret_cast<u64*>(pg.next)[i] = last + 1;
-      const u32 start = ipos & 0xFFFFu, count = ipos >> 16;
-      u32 nxt = start + count;
-      if (nxt >= K) nxt -= K;
-      if (nxt < K) reinterpret_cast<u64*>(pg.infl_buf)[i * K + nxt] = last;  // (the ring's invariant)
-      pg.infl_pos[i] = start | ((count + 1) << 16);
-    } else {
-      pg.pstate[i] = u8(st | QB_PR_PROBE_SENT);
-    }
-  }
-  return QB_MSG_APP;
+  return maybe_send_append(A.pg, r.g, i, nx, st, ipos, r.first, r.last, r.ments,
+                           [&] { return term_at(A, r, nx - 1); },
+                           reinterpret_cast<u64*>(A.out.msg_index) + i,
+                           reinterpret_cast<u64*>(A.out.msg_log_term) + i,
+                           reinterpret_cast<u64*>(A.out.msg_n) + i);
 }
 
 __device__ __forceinline__ u64 wave_sum64(u64 v) {
@@ -174,11 +105,10 @@ __global__ __launch_bounds__(kBlock) void k_propose(Args A) {
   u64 ents = 0;  // entries this thread's groups appended
 
   for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const u64 g0 = tile * kBlock;
-    const u64 g = g0 + tid;
-    const u64 gend = g0 + kBlock < G ? g0 + kBlock : G;
+    SpanTile S(tile, G);
+    const u64 g = S.g0 + tid;
     const bool live = g < G;
-    const u32 sb = pg.off[g0], se = pg.off[gend];  // the tile's span (used in P2 only)
+    const u32 sb = pg.off[S.g0], se = pg.off[S.gend];  // the tile's span (used in P2 only)
 
     // ------------------------------------------------------------- P1 ---
     const u8 action = live ? A.in.action[g] : u8(0);
@@ -203,7 +133,7 @@ __global__ __launch_bounds__(kBlock) void k_propose(Args A) {
       const u64 pay = reinterpret_cast<const u64*>(A.in.payload)[g], unc0 = unc_a[g];
       const u64 ments = reinterpret_cast<const u64*>(pg.max_ents)[g];
       const u64 first = reinterpret_cast<const u64*>(pg.first_index)[g];
-      ns = s1 > s0 ? (s1 - s0 < QB_MAX_SLOTS ? s1 - s0 : u32(QB_MAX_SLOTS)) : 0u;
+      ns = clamp_slots(s0, s1);
       const u32 state = role & 3u;
       const bool entries = code == QB_PROP_ENTRIES;
       if (state != QB_ROLE_LEADER) {
@@ -225,17 +155,16 @@ __global__ __launch_bounds__(kBlock) void k_propose(Args A) {
           pf = QB_PFLAG_DROPPED;
         }
       } else {
-        u32 nruns = (meta >> 16) & 0xFu;
-        nruns = nruns < 1u ? 1u : (nruns > QB_LEADER_MAX_RUNS ? u32(QB_LEADER_MAX_RUNS) : nruns);
+        const u32 nruns = meta_nruns(meta);
         const bool newrun = lt0 != term;
-        const u32 oslot = meta & 0xFFu;
+        const u32 oslot = meta_own_slot(meta);
         if (entries && n == 0) {  // raft.go:1020-1022
           empty = true;
           pf = QB_PFLAG_BAD;
         } else if (entries && oslot >= ns) {  // raft.go:1023-1028
           d_noprog = true;
           pf = QB_PFLAG_DROPPED;
-        } else if (entries && ((meta >> 8) & 0xFFu) != 0xFFu) {  // raft.go:1029-1032
+        } else if (entries && meta_transferee(meta) != 0xFFu) {  // raft.go:1029-1032
           d_transfer = true;
           pf = QB_PFLAG_DROPPED;
         } else if (newrun && nruns == QB_LEADER_MAX_RUNS) {
@@ -252,7 +181,7 @@ __global__ __launch_bounds__(kBlock) void k_propose(Args A) {
               if (at < n) {
                 const u64 pci = pci_a[g];
                 const u64 applied = reinterpret_cast<const u64*>(pg.applied)[g];
-                const bool joint = (cfg >> 16) != 0;
+                const bool joint = cfg_outgoing(cfg) != 0;
                 const bool leave = (action & QB_PROP_CC_LEAVE_JOINT) != 0;
                 if (pci > applied || joint != leave) {
                   cc_ref = true;
@@ -305,7 +234,7 @@ __global__ __launch_bounds__(kBlock) void k_propose(Args A) {
               if (nx0 < last1 + 1) next_a[io] = last1 + 1;
               // maybeCommit (raft.go:585-588).  First whether every non-empty
               // half has a quorum above committed at all: one pass over match.
-              const u32 min_ = cfg & 0xFFFFu, mout = cfg >> 16;
+              const u32 min_ = cfg_incoming(cfg), mout = cfg_outgoing(cfg);
               int cin = 0, cout = 0;
               for (u32 k = 0; k < ns; ++k) {
                 const u64 mk = k == oslot ? ownm : match_a[u64(s0) + k];
@@ -354,16 +283,10 @@ __global__ __launch_bounds__(kBlock) void k_propose(Args A) {
     // ------------------------------------------------------------- P2 ---
     const bool fires = __syncthreads_or(fl != 0);  // (also: the previous tile's LDS is free)
     if (fires) {
-      const u32 span = se - sb;
-      const bool staged = se >= sb && span <= kSpanCap;  // workgroup-uniform
-      if (staged) {
-        const u32 j0 = s0 - sb;
-        // a staged group's slots lie inside the span for any monotone off; one
-        // that does not (a malformed table) sends nothing
-        if (fl && !(s0 >= sb && j0 <= span && ns <= span - j0)) ns = 0;
+      S.bound(sb, se);
+      if (S.staged) {
         if (fl) {
-          T.j0[tid] = j0;
-          T.ns[tid] = u8(ns);
+          ns = T.slots.claim(S, s0, ns);
           T.own[tid] = u8(own);
           T.nruns[tid] = u8(rc.nruns);
           T.last[tid] = rc.last;
@@ -372,46 +295,43 @@ __global__ __launch_bounds__(kBlock) void k_propose(Args A) {
           T.oldt[tid] = rc.oldt;
           T.ments[tid] = rc.ments;
           T.first[tid] = rc.first;
-          for (u32 k = 0; k < ns; ++k) T.owner[j0 + k] = u8(tid);
         }
         T.fl[tid] = fl;
         __syncthreads();
-        for (u32 jb = tid; jb < span; jb += kBlock * kUnroll) {
+        for (u32 jb = tid; jb < S.span; jb += kBlock * kSpanUnroll) {
           // the trip's slot words first, then the sends
-          u32 t_[kUnroll], ip[kUnroll];
-          u64 nx[kUnroll];
-          u8 st[kUnroll], what[kUnroll];  // what: 0 not ours, 1 a peer, 2 the own slot
+          u32 t_[kSpanUnroll], ip[kSpanUnroll];
+          u64 nx[kSpanUnroll];
+          u8 st[kSpanUnroll], what[kSpanUnroll];  // what: 0 not ours, 1 a peer, 2 the own slot
 #pragma unroll
-          for (u32 u = 0; u < kUnroll; ++u) {
+          for (u32 u = 0; u < kSpanUnroll; ++u) {
             const u32 j = jb + u * kBlock;
             what[u] = 0;
             t_[u] = 0;
             ip[u] = 0;
             nx[u] = 0;
             st[u] = 0;
-            if (j >= span) continue;
-            // a slot no broadcasting group owns holds a stale owner byte: the
-            // named owner's own range decides
-            const u32 t = T.owner[j];
-            const u32 k = j - T.j0[t];
-            if (!T.fl[t] || k >= T.ns[t]) continue;
+            if (j >= S.span) continue;
+            const SpanOwners::Slot o = T.slots.find(j);
+            const u32 t = o.t;
+            if (!T.fl[t] || !o.in) continue;
             t_[u] = t;
-            what[u] = k == T.own[t] ? 2 : 1;
+            what[u] = o.k == T.own[t] ? 2 : 1;
             if (what[u] == 1) {
-              const u64 i = u64(sb) + j;
+              const u64 i = u64(S.sb) + j;
               nx[u] = next_a[i];
               st[u] = pg.pstate[i];
               ip[u] = pg.infl_pos[i];
             }
           }
 #pragma unroll
-          for (u32 u = 0; u < kUnroll; ++u) {
+          for (u32 u = 0; u < kSpanUnroll; ++u) {
             if (!what[u]) continue;
-            const u64 i = u64(sb) + jb + u * kBlock;
+            const u64 i = u64(S.sb) + jb + u * kBlock;
             u32 mt = 0;
             if (what[u] == 1) {
               const u32 t = t_[u];
-              const Recipe r{g0 + t, T.last[t], T.old[t], T.term[t], T.oldt[t], T.ments[t],
+              const Recipe r{S.g0 + t, T.last[t], T.old[t], T.term[t], T.oldt[t], T.ments[t],
                              T.first[t], T.nruns[t]};
               mt = send_slot(A, r, i, nx[u], st[u], ip[u]);
               napp += mt == QB_MSG_APP;
@@ -457,27 +377,8 @@ __global__ __launch_bounds__(kBlock) void k_propose(Args A) {
   ents = wave_sum64(ents);  // (u64: a block's entries can pass 2^32)
   if ((tid & 63) == 0 && ents) atomicAdd(&T.ents, ents);
   __syncthreads();
-  const int slot[QB_PSTAT_COUNT] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18};
-  BlockTally<QB_PSTAT_COUNT>::publish(T.tally, reinterpret_cast<u64*>(A.stats), slot);
+  BlockTally<QB_PSTAT_COUNT>::publish(T.tally, reinterpret_cast<u64*>(A.stats));
   if (tid == 0 && T.ents) atomicAdd(reinterpret_cast<u64*>(A.stats) + QB_PSTAT_ENTRIES, T.ents);
-}
-
-// The grid's cap: the workgroups the device holds at once (occupancy x CUs);
-// kPropBlocks if the runtime will not say.  Asked once per process.
-inline unsigned resident_blocks() {
-  static const unsigned n = [] {
-    int dev = 0, per_cu = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_propose, kBlock, 0) != hipSuccess ||
-        per_cu <= 0 || cus <= 0) {
-      (void)hipGetLastError();
-      return kPropBlocks;
-    }
-    const unsigned r = unsigned(per_cu) * unsigned(cus);
-    return r < kPropBlocks ? r : kPropBlocks;
-  }();
-  return n;
 }
 
 }  // namespace propose
@@ -509,9 +410,8 @@ extern "C" int qb_dev_leader_propose(const qb_propose_groups* pg, const qb_propo
              "qb_dev_leader_propose: required output pointer is NULL (pflags / msg_type / "
              "msg_index / msg_log_term / msg_n / stats)");
   propose::Args A{*pg, *in, *out, reinterpret_cast<u64*>(stats)};
-  const unsigned tiles = grid_for(pg->G), cap = propose::resident_blocks();
-  hipLaunchKernelGGL(propose::k_propose, dim3(tiles < cap ? tiles : cap), dim3(kBlock), 0,
-                     as_stream(stream), A);
+  hipLaunchKernelGGL(propose::k_propose, dim3(stream_grid<propose::k_propose>(pg->G)),
+                     dim3(kBlock), 0, as_stream(stream), A);
   QB_CHECK_LAUNCH("k_propose");
   return QB_OK;
 }

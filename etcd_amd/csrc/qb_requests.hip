@@ -6,35 +6,25 @@
 // other halves live in qb_leader.hip, qb_tick.hip, qb_follower.hip and
 // qb_campaign.hip.
 //
-// One kernel, a streaming pass with no cross-group dependence, the shape of
-// k_campaign / k_propose.  A workgroup takes tiles of 256 consecutive groups,
-// which own one contiguous slot span [off[g0], off[g0 + 256]):
+// One kernel in the span-tile shape (qb_span_tile.h):
 //   P1  thread per group: the two request bytes first; a group with neither a
 //       read nor a transfer writes qflags and xf_type and is done.  An acting
 //       group requests all its group words at once (one HBM round trip),
 //       applies its reads in k order (the queue's contexts read four at a
 //       time; the run table only when committed lies before the last run),
 //       then the transfer, whose single sendAppend runs here.  A group that
-//       broadcasts names itself owner of its slots in LDS (one byte per slot
-//       of the span) and leaves committed and its own slot there.
-//   P2  (only if a group of the tile broadcasts) the workgroup strides the
-//       span with a thread per slot: match read and hb_commit written as
-//       coalesced runs.  Slots of groups that do not broadcast touch nothing.
-// A span wider than kSpanCap (a table with gaps) runs P2 with each thread
-// looping over its own group's slots in the global arrays.
+//       broadcasts claims its slots and leaves committed and its own slot in
+//       LDS.
+//   P2  (only if a group of the tile broadcasts) match read and hb_commit
+//       written.
 //
-// maybeSendAppend is restated here from qb_propose.hip (as that file restates
-// qb_leader.hip's).  Statistics go through BlockTally, the per-read outcomes
-// through a packed per-thread count first; the grid is capped at the
-// workgroups the device holds at once.
-#include "qb_common.h"
+// The per-read outcomes go through a packed per-thread count before the
+// BlockTally.
+#include "qb_span_tile.h"
 
 namespace qb {
 namespace requests {
 
-constexpr u32 kSpanCap = kBlock * QB_MAX_SLOTS;  // 4096: every well-formed tile
-constexpr unsigned kReqBlocks = 2048;
-constexpr u32 kUnroll = 4;  // slots per thread and trip
 constexpr u32 kNone = 0xFFFFFFFFu;
 constexpr u32 kNoSlot = 0xFFu;
 constexpr u32 kReadCodes = QB_RD_BAD;  // rd_status codes 1..11 -> stats 0..10
@@ -53,31 +43,18 @@ struct Log {
 };
 
 struct Tile {
-  u8 owner[kSpanCap];  // slot of the span -> thread (group) of the tile
+  SpanOwners slots;
   u64 committed[kBlock];
-  u32 j0[kBlock];      // the group's first slot within the span
-  u8 ns[kBlock];       // its slot count (<= QB_MAX_SLOTS)
-  u8 fl[kBlock];       // non-zero: the group broadcasts
+  u8 fl[kBlock];      // non-zero: the group broadcasts
   u8 own[kBlock];      // own slot, 0xFF = the leader has no Progress
   u32 tally[QB_QSTAT_COUNT];
 };
 
-// raftLog.term (log.go:268-288) + zeroTermOnErrCompacted.  `upto` runs of the
-// table are walked (those that can start at or below i).
-__device__ __forceinline__ u64 walk_runs(const Args& A, const Log& l, u64 i, u32 upto) {
-  const u64 G = A.rg.G;
-  const u64* rs = reinterpret_cast<const u64*>(A.rg.run_start) + l.g;  // run q at rs[q * G]
-  const u64* rt = reinterpret_cast<const u64*>(A.rg.run_term) + l.g;
-  u64 t = 0;
-  for (u32 q = 0; q < upto; ++q)
-    if (rs[q * G] <= i) t = rt[q * G];
-  return t;
-}
-
+// raftLog.term (log.go:268-288) + zeroTermOnErrCompacted.
 __device__ __forceinline__ u64 term_at(const Args& A, const Log& l, u64 i) {
   if (i < l.first - 1 || i > l.last) return 0;
   if (i == l.last) return l.lastt;
-  return walk_runs(A, l, i, l.nruns);
+  return walk_runs(A.rg.run_start, A.rg.run_term, A.rg.G, l.g, i, l.nruns);
 }
 
 // term(committed): from the last run's start on it is last_term, and only an
@@ -87,66 +64,17 @@ __device__ __forceinline__ u64 term_of_committed(const Args& A, const Log& l, u6
   if (com == l.last || l.nruns == 1) return l.lastt;
   const u64 lrs = reinterpret_cast<const u64*>(A.rg.run_start)[u64(l.nruns - 1) * A.rg.G + l.g];
   if (com >= lrs) return l.lastt;
-  return walk_runs(A, l, com, l.nruns - 1);
+  return walk_runs(A.rg.run_start, A.rg.run_term, A.rg.G, l.g, com, l.nruns - 1);
 }
 
-// maybeSendAppend(to, true) (raft.go:432-492) on slot i of group l.g; the
-// message goes to the group's xf_* words.  Returns the message type (0: none).
+// maybeSendAppend on slot i of group l.g, the message to the group's xf_* words.
 __device__ __forceinline__ u32 send_slot(const Args& A, const Log& l, u64 ments, u64 i) {
-  const qb_request_groups& rg = A.rg;
-  const u32 K = rg.inflight_cap;
-  const u64 nx = reinterpret_cast<const u64*>(rg.next)[i];
-  const u8 st = rg.pstate[i];
-  const u32 ipos = rg.infl_pos[i];
-  const u32 state = st & 3u;
-  // IsPaused (progress.go:193-212)
-  if (state == QB_PR_PROBE ? (st & QB_PR_PROBE_SENT) != 0
-                           : (state == QB_PR_REPLICATE ? (ipos >> 16) == K : true))
-    return 0;
-  const u64 lt = term_at(A, l, nx - 1);
-  u64 n = 0;
-  bool compacted = false;
-  if (nx <= l.last) {
-    if (nx < l.first) compacted = true;  // ErrCompacted
-    else {
-      const u64 avail = l.last - nx + 1;
-      n = avail < ments ? avail : ments;
-    }
-  }
-  u64* __restrict__ mi = reinterpret_cast<u64*>(A.out.xf_index);
-  u64* __restrict__ ml = reinterpret_cast<u64*>(A.out.xf_log_term);
-  u64* __restrict__ mn = reinterpret_cast<u64*>(A.out.xf_n);
-  if (compacted) {
-    if (!(st & QB_PR_RECENT_ACTIVE)) return 0;
-    const u64 snapi = reinterpret_cast<const u64*>(rg.snap_index)[l.g];
-    if (snapi == 0) return 0;  // ErrSnapshotTemporarilyUnavailable
-    mi[l.g] = snapi;
-    ml[l.g] = reinterpret_cast<const u64*>(rg.snap_term)[l.g];
-    mn[l.g] = 0;
-    // BecomeSnapshot (progress.go:139-144)
-    rg.pstate[i] = u8((st & QB_PR_RECENT_ACTIVE) | QB_PR_SNAPSHOT);
-    reinterpret_cast<u64*>(rg.pending_snapshot)[i] = snapi;
-    rg.infl_pos[i] = 0;
-    return QB_MSG_SNAP;
-  }
-  mi[l.g] = nx - 1;
-  ml[l.g] = lt;
-  mn[l.g] = n;
-  if (n != 0) {
-    if (state == QB_PR_REPLICATE) {
-      // OptimisticUpdate (progress.go:159-161), Inflights.Add (inflights.go:55-70)
-      const u64 last = nx + n - 1;
-      reinterpret_cast<u64*>(rg.next)[i] = last + 1;
-      const u32 start = ipos & 0xFFFFu, count = ipos >> 16;
-      u32 nxt = start + count;
-      if (nxt >= K) nxt -= K;
-      if (nxt < K) reinterpret_cast<u64*>(rg.infl_buf)[i * K + nxt] = last;  // (the ring's invariant)
-      rg.infl_pos[i] = start | ((count + 1) << 16);
-    } else {
-      rg.pstate[i] = u8(st | QB_PR_PROBE_SENT);
-    }
-  }
-  return QB_MSG_APP;
+  const u64 nx = reinterpret_cast<const u64*>(A.rg.next)[i];
+  return maybe_send_append(A.rg, l.g, i, nx, A.rg.pstate[i], A.rg.infl_pos[i], l.first, l.last,
+                           ments, [&] { return term_at(A, l, nx - 1); },
+                           reinterpret_cast<u64*>(A.out.xf_index) + l.g,
+                           reinterpret_cast<u64*>(A.out.xf_log_term) + l.g,
+                           reinterpret_cast<u64*>(A.out.xf_n) + l.g);
 }
 
 __global__ __launch_bounds__(kBlock) void k_requests(Args A) {
@@ -168,11 +96,10 @@ __global__ __launch_bounds__(kBlock) void k_requests(Args A) {
   for (u32 c = 0; c < kReadCodes; ++c) racc[c] = 0;
 
   for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const u64 g0 = tile * kBlock;
-    const u64 g = g0 + tid;
-    const u64 gend = g0 + kBlock < G ? g0 + kBlock : G;
+    SpanTile S(tile, G);
+    const u64 g = S.g0 + tid;
     const bool live = g < G;
-    const u32 sb = rg.off[g0], se = rg.off[gend];  // the tile's span (used in P2 only)
+    const u32 sb = rg.off[S.g0], se = rg.off[S.gend];  // the tile's span (used in P2 only)
 
     // ------------------------------------------------------------- P1 ---
     u32 nr = live ? u32(A.in.n_reads[g]) : 0u;
@@ -199,15 +126,13 @@ __global__ __launch_bounds__(kBlock) void k_requests(Args A) {
       com = reinterpret_cast<const u64*>(rg.committed)[g];
       const u64 mterm = (xfrom != kNoSlot && A.in.xf_term)
                             ? reinterpret_cast<const u64*>(A.in.xf_term)[g] : 0ull;
-      u32 nruns = (meta0 >> 16) & 0xFu;
-      nruns = nruns < 1u ? 1u : (nruns > QB_LEADER_MAX_RUNS ? u32(QB_LEADER_MAX_RUNS) : nruns);
       const Log lg{g, reinterpret_cast<const u64*>(rg.first_index)[g],
                    reinterpret_cast<const u64*>(rg.last_index)[g],
-                   reinterpret_cast<const u64*>(rg.last_term)[g], nruns};
-      ns = s1 > s0 ? (s1 - s0 < QB_MAX_SLOTS ? s1 - s0 : u32(QB_MAX_SLOTS)) : 0u;
+                   reinterpret_cast<const u64*>(rg.last_term)[g], meta_nruns(meta0)};
+      ns = clamp_slots(s0, s1);
       const u32 state = role & 3u;
-      const u32 min_ = cfg & 0xFFFFu, mout = cfg >> 16;
-      const u32 oslot = meta0 & 0xFFu;
+      const u32 min_ = cfg_incoming(cfg), mout = cfg_outgoing(cfg);
+      const u32 oslot = meta_own_slot(meta0);
       ls = oslot < ns ? oslot : kNoSlot;
       u32 meta = meta0;
 
@@ -217,7 +142,7 @@ __global__ __launch_bounds__(kBlock) void k_requests(Args A) {
           const bool single = __popc(min_) == 1 && mout == 0;  // IsSingleton, tracker.go:228-230
           const bool cur = single || term_of_committed(A, lg, com) == term;  // raft.go:1731-1733
           const u32 ownbit = oslot < 16u ? 1u << oslot : 0u;
-          u32 nq = (meta0 >> 20) & 0x1Fu;
+          u32 nq = meta_readq_len(meta0);
           if (nq > cap) nq = cap;
           const u32 nq0 = nq;
           u64* qctx = reinterpret_cast<u64*>(rg.rq_ctx) + g * cap;
@@ -301,7 +226,7 @@ __global__ __launch_bounds__(kBlock) void k_requests(Args A) {
           } else if (!(((min_ | mout) >> xfrom) & 1u)) {
             x_learner = true;
           } else {
-            const u32 pending = (meta >> 8) & 0xFFu;
+            const u32 pending = meta_transferee(meta);
             bool go = true;
             if (pending != kNoSlot) {
               if (pending == xfrom) {
@@ -348,45 +273,36 @@ __global__ __launch_bounds__(kBlock) void k_requests(Args A) {
     // ------------------------------------------------------------- P2 ---
     const bool fires = __syncthreads_or(fl != 0);  // (also: the previous tile's LDS is free)
     if (fires) {
-      const u32 span = se - sb;
-      const bool staged = se >= sb && span <= kSpanCap;  // workgroup-uniform
-      if (staged) {
-        const u32 j0 = s0 - sb;
-        // a staged group's slots lie inside the span for any monotone off; one
-        // that does not (a malformed table) writes no heartbeat
-        if (fl && !(s0 >= sb && j0 <= span && ns <= span - j0)) ns = 0;
+      S.bound(sb, se);
+      if (S.staged) {
         if (fl) {
-          T.j0[tid] = j0;
-          T.ns[tid] = u8(ns);
+          ns = T.slots.claim(S, s0, ns);
           T.own[tid] = u8(ls);
           T.committed[tid] = com;
-          for (u32 k = 0; k < ns; ++k) T.owner[j0 + k] = u8(tid);
         }
         T.fl[tid] = fl;
         __syncthreads();
-        for (u32 jb = tid; jb < span; jb += kBlock * kUnroll) {
-          u64 m[kUnroll], c[kUnroll];
-          bool on[kUnroll];
+        for (u32 jb = tid; jb < S.span; jb += kBlock * kSpanUnroll) {
+          u64 m[kSpanUnroll], c[kSpanUnroll];
+          bool on[kSpanUnroll];
 #pragma unroll
-          for (u32 u = 0; u < kUnroll; ++u) {
+          for (u32 u = 0; u < kSpanUnroll; ++u) {
             const u32 j = jb + u * kBlock;
             on[u] = false;
             m[u] = c[u] = 0;
-            if (j >= span) continue;
-            // a slot no broadcasting group owns holds a stale owner byte: the
-            // named owner's own range decides
-            const u32 t = T.owner[j];
-            const u32 k = j - T.j0[t];
-            if (!T.fl[t] || k >= T.ns[t] || k == T.own[t]) continue;
+            if (j >= S.span) continue;
+            const SpanOwners::Slot o = T.slots.find(j);
+            const u32 t = o.t;
+            if (!T.fl[t] || !o.in || o.k == T.own[t]) continue;
             on[u] = true;  // sendHeartbeat, raft.go:495-511
             c[u] = T.committed[t];
-            m[u] = __builtin_nontemporal_load(match + u64(sb) + j);
+            m[u] = __builtin_nontemporal_load(match + u64(S.sb) + j);
           }
 #pragma unroll
-          for (u32 u = 0; u < kUnroll; ++u)
+          for (u32 u = 0; u < kSpanUnroll; ++u)
             if (on[u])
               __builtin_nontemporal_store(m[u] < c[u] ? m[u] : c[u],
-                                          hb_commit + u64(sb) + jb + u * kBlock);
+                                          hb_commit + u64(S.sb) + jb + u * kBlock);
         }
       } else if (fl) {
         for (u32 k = 0; k < ns; ++k) {
@@ -418,31 +334,11 @@ __global__ __launch_bounds__(kBlock) void k_requests(Args A) {
   __syncthreads();  // T.tally zeroed; the last tile's LDS reads done
   tally.stage(T.tally);
   __syncthreads();
-  const int slot[QB_QSTAT_COUNT] = {0,  1,  2,  3,  4,  5,  6,  7,  8,  9,  10, 11, 12, 13,
-                                    14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26};
-  BlockTally<QB_QSTAT_COUNT>::publish(T.tally, reinterpret_cast<u64*>(A.stats), slot);
+  BlockTally<QB_QSTAT_COUNT>::publish(T.tally, reinterpret_cast<u64*>(A.stats));
 }
 
 static_assert(QB_QSTAT_READ_STATES == QB_RD_READ_STATE - 1 && QB_QSTAT_BAD_CTX == QB_RD_BAD - 1,
               "the read counters follow the rd_status codes");
-
-// The grid's cap: the workgroups the device holds at once (occupancy x CUs);
-// kReqBlocks if the runtime will not say.  Asked once per process.
-inline unsigned resident_blocks() {
-  static const unsigned n = [] {
-    int dev = 0, per_cu = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_requests, kBlock, 0) != hipSuccess ||
-        per_cu <= 0 || cus <= 0) {
-      (void)hipGetLastError();
-      return kReqBlocks;
-    }
-    const unsigned r = unsigned(per_cu) * unsigned(cus);
-    return r < kReqBlocks ? r : kReqBlocks;
-  }();
-  return n;
-}
 
 }  // namespace requests
 }  // namespace qb
@@ -479,9 +375,8 @@ extern "C" int qb_dev_leader_requests(const qb_request_groups* rg, const qb_requ
              "qb_dev_leader_requests: required output pointer is NULL (rd_status / rd_index / "
              "hb_commit / xf_type / xf_index / xf_log_term / xf_n / qflags / stats)");
   requests::Args A{*rg, *in, *out, reinterpret_cast<u64*>(stats)};
-  const unsigned tiles = grid_for(rg->G), cap = requests::resident_blocks();
-  hipLaunchKernelGGL(requests::k_requests, dim3(tiles < cap ? tiles : cap), dim3(kBlock), 0,
-                     as_stream(stream), A);
+  hipLaunchKernelGGL(requests::k_requests, dim3(stream_grid<requests::k_requests>(rg->G)),
+                     dim3(kBlock), 0, as_stream(stream), A);
   QB_CHECK_LAUNCH("k_requests");
   return QB_OK;
 }

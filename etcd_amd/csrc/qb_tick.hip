@@ -3,44 +3,33 @@
 // MsgCheckQuorum steps of stepLeader (raft.go:994-1018) and the part of
 // becomeFollower -> reset (raft.go:590-619) that touches the tick's fields.
 //
-// One kernel, a streaming pass with no cross-group dependence.  A workgroup
-// takes tiles of 256 consecutive groups, which own one contiguous slot span
-// [off[g0], off[g0 + 256]):
+// One kernel in the span-tile shape (qb_span_tile.h), with two slot phases:
 //   P1  thread per group: role and timers; a non-leader finishes here
 //       (tickElection).  A leader decides whether this tick sweeps
 //       (electionElapsed >= election_timeout with check_quorum) and whether
-//       it may beat, loads only the group words those need, and names itself
-//       owner of its slots in LDS (one byte per slot of the span).
-//   P2  (only if a group of the tile sweeps) the workgroup strides the span:
-//       the pstate bytes of sweeping groups, read as coalesced runs, kept in
-//       LDS and folded into the group's 16-bit RecentActive mask (LDS atomic
-//       OR).  Slots of groups that do not sweep issue no load.
+//       it may beat, loads only the group words those need, and claims its
+//       slots.
+//   P2  (only if a group of the tile sweeps) the span's pstate bytes of
+//       sweeping groups, kept in LDS and folded into the group's 16-bit
+//       RecentActive mask (LDS atomic OR).
 //   P3  thread per group: QuorumActive on the mask (tracker.go:215-225),
 //       step-down, transfer abort, beat; timers, role, meta, tflags, hb_ctx
 //       written; committed / leader slot / slot action left in LDS.
-//   P4  the workgroup strides the span again: RecentActive bytes that change
-//       are stored, and beating groups read match and write hb_commit, both
-//       as coalesced runs.  Slots of groups that fire nothing touch nothing.
+//   P4  the span again: RecentActive bytes that change are stored, and
+//       beating groups read match and write hb_commit.
 // A tile whose groups fire nothing (no sweep, no beat) skips P2 and P4 and
-// their barriers: it reads no slot data.  A span wider than kSpanCap — only a table
-// with gaps or groups above QB_MAX_SLOTS slots, which are read as
-// QB_MAX_SLOTS, can produce one: 256 well-formed groups own at most 4096
-// slots — runs P2 / P4 with each thread looping over its own group's slots
-// in the global arrays.
+// their barriers: it reads no slot data.
 //
-// Statistics are tallied per wave, reduced per workgroup in LDS and flushed
-// with one global atomic per counter per workgroup (BlockTally); the grid is
-// capped at the workgroups the device holds at once (at most kTickBlocks),
-// striding the tiles, so that flush stays a few thousand atomics however
-// large G is.
-#include "qb_common.h"
+// The owner map is written out here, not taken from SpanOwners: with its LDS
+// arrays regrouped into that struct and find() in the two loops this kernel
+// measured 2 us (1.5 %) slower per tick in each of four alternating rounds,
+// with claim() after the first barrier as well 3 %.  The guard, the claim loop
+// and the stale-owner rule below are those of SpanOwners::claim and ::find; a
+// change to either is made here too.
+#include "qb_span_tile.h"
 
 namespace qb {
 namespace tick {
-
-constexpr u32 kSpanCap = kBlock * QB_MAX_SLOTS;  // 4096: every well-formed tile
-constexpr unsigned kTickBlocks = 2048;
-constexpr u32 kUnroll = 4;  // slots per thread whose loads are in flight together
 
 // slot actions of a group (LDS, one byte per group of the tile)
 constexpr u8 kActSweep = 1;   // P2: collect RecentActive; P4: clear it
@@ -80,9 +69,8 @@ __global__ __launch_bounds__(kBlock) void k_tick(Args A) {
   if (tid < QB_TSTAT_COUNT) T.tally[tid] = 0;
 
   for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const u64 g0 = tile * kBlock;
-    const u64 g = g0 + tid;
-    const u64 gend = g0 + kBlock < G ? g0 + kBlock : G;
+    SpanTile S(tile, G);
+    const u64 g = S.g0 + tid;
     const bool live = g < G;
 
     // ------------------------------------------------------------- P1 ---
@@ -102,10 +90,10 @@ __global__ __launch_bounds__(kBlock) void k_tick(Args A) {
       const u32 s1 = tg.off[g + 1];
       meta = tg.meta[g];
       com = reinterpret_cast<const u64*>(tg.committed)[g];
-      ns = s1 > s0 ? (s1 - s0 < QB_MAX_SLOTS ? s1 - s0 : u32(QB_MAX_SLOTS)) : 0u;
+      ns = clamp_slots(s0, s1);
       leader = (role & 3u) == QB_ROLE_LEADER;
     }
-    const u32 sb = tg.off[g0];
+    const u32 sb = tg.off[S.g0];
     if (live && !leader) {  // tickElection, raft.go:645-654
       if ((role & QB_ROLE_PROMOTABLE) && ee >= tg.rand_timeout[g]) {  // raft.go:648, 1714-1716
         ee = 0;
@@ -122,8 +110,9 @@ __global__ __launch_bounds__(kBlock) void k_tick(Args A) {
       }
       if (he >= ht) act |= kActBeat;  // (withdrawn in P3 if the leader steps down)
     }
-    const u32 span = tg.off[gend] - sb;
-    const bool staged = tg.off[gend] >= sb && span <= kSpanCap;  // workgroup-uniform
+    S.bound(sb, tg.off[S.gend]);
+    const u32 span = S.span;
+    const bool staged = S.staged;
     const u32 j0 = s0 - sb;
     // a staged group's slots lie inside the span for any monotone off; one
     // that does not (a malformed table) acts on no slot
@@ -143,12 +132,12 @@ __global__ __launch_bounds__(kBlock) void k_tick(Args A) {
       if (anysweep) {
         if (staged) {
           // four slots per thread and trip: the loads are issued together
-          for (u32 jb = tid; jb < span; jb += kBlock * kUnroll) {
-            u32 own_t[kUnroll], bit[kUnroll];
-            u8 st[kUnroll];
-            bool on[kUnroll];
+          for (u32 jb = tid; jb < span; jb += kBlock * kSpanUnroll) {
+            u32 own_t[kSpanUnroll], bit[kSpanUnroll];
+            u8 st[kSpanUnroll];
+            bool on[kSpanUnroll];
 #pragma unroll
-            for (u32 u = 0; u < kUnroll; ++u) {
+            for (u32 u = 0; u < kSpanUnroll; ++u) {
               const u32 j = jb + u * kBlock;
               on[u] = false;
               st[u] = 0;
@@ -164,7 +153,7 @@ __global__ __launch_bounds__(kBlock) void k_tick(Args A) {
               }
             }
 #pragma unroll
-            for (u32 u = 0; u < kUnroll; ++u) {
+            for (u32 u = 0; u < kSpanUnroll; ++u) {
               if (!on[u]) continue;
               T.st[jb + u * kBlock] = st[u];
               if (st[u] & QB_PR_RECENT_ACTIVE) atomicOr(&T.active[own_t[u]], bit[u]);
@@ -182,7 +171,7 @@ __global__ __launch_bounds__(kBlock) void k_tick(Args A) {
     // ------------------------------------------------------------- P3 ---
     bool beat = false;
     u32 nhb = 0;
-    const u32 ls = (meta & 0xFFu) < ns ? (meta & 0xFFu) : 0xFFu;  // raft.go:1004: own Progress
+    const u32 ls = meta_own_slot(meta) < ns ? meta_own_slot(meta) : 0xFFu;  // raft.go:1004: own Progress
     if (leader) {
       bool down = false;
       if (sweep) {  // raft.go:661
@@ -196,10 +185,10 @@ __global__ __launch_bounds__(kBlock) void k_tick(Args A) {
           role = u8(role & ~3u);  // QB_ROLE_FOLLOWER
           he = 0;
           tf |= QB_TFLAG_STEPPED_DOWN;
-          if ((meta & 0xFF00u) != 0xFF00u) tg.meta[g] = meta | 0xFF00u;
+          if (meta_transferee(meta) != 0xFFu) tg.meta[g] = meta | 0xFF00u;
           tg.role[g] = role;
           act = kActSweep | kActDown;  // no beat: raft.go:674-676
-        } else if ((meta & 0xFF00u) != 0xFF00u) {  // raft.go:669-671
+        } else if (meta_transferee(meta) != 0xFFu) {  // raft.go:669-671
           tg.meta[g] = meta | 0xFF00u;
           tf |= QB_TFLAG_TRANSFER_ABORTED;
         }
@@ -210,7 +199,7 @@ __global__ __launch_bounds__(kBlock) void k_tick(Args A) {
         tf |= QB_TFLAG_BEAT;
         nhb = ns - (ls != 0xFFu ? 1u : 0u);
         // bcastHeartbeat, raft.go:524-531: lastPendingRequestCtx
-        u32 nq = (meta >> 20) & 0x1Fu;
+        u32 nq = meta_readq_len(meta);
         if (nq > tg.readq_cap) nq = tg.readq_cap;
         A.hb_ctx[g] = nq ? reinterpret_cast<const u64*>(tg.rq_ctx)[g * tg.readq_cap + nq - 1] : 0ull;
       }
@@ -228,11 +217,11 @@ __global__ __launch_bounds__(kBlock) void k_tick(Args A) {
       }
       __syncthreads();
       if (staged) {
-        for (u32 jb = tid; jb < span; jb += kBlock * kUnroll) {
-          u64 m[kUnroll], c[kUnroll];
-          u8 op[kUnroll], nst[kUnroll];  // op: 1 store the state byte, 2 store the heartbeat
+        for (u32 jb = tid; jb < span; jb += kBlock * kSpanUnroll) {
+          u64 m[kSpanUnroll], c[kSpanUnroll];
+          u8 op[kSpanUnroll], nst[kSpanUnroll];  // op: 1 store the state byte, 2 store the heartbeat
 #pragma unroll
-          for (u32 u = 0; u < kUnroll; ++u) {
+          for (u32 u = 0; u < kSpanUnroll; ++u) {
             const u32 j = jb + u * kBlock;
             op[u] = 0;
             if (j >= span) continue;
@@ -254,7 +243,7 @@ __global__ __launch_bounds__(kBlock) void k_tick(Args A) {
             }
           }
 #pragma unroll
-          for (u32 u = 0; u < kUnroll; ++u) {
+          for (u32 u = 0; u < kSpanUnroll; ++u) {
             const u64 j = u64(sb) + jb + u * kBlock;
             if (op[u] & 1) tg.pstate[j] = nst[u];
             if (op[u] & 2) __builtin_nontemporal_store(m[u] < c[u] ? m[u] : c[u], A.hb_commit + j);
@@ -288,27 +277,7 @@ __global__ __launch_bounds__(kBlock) void k_tick(Args A) {
   __syncthreads();  // T.tally zeroed; the last tile's LDS reads done
   tally.stage(T.tally);
   __syncthreads();
-  const int slot[QB_TSTAT_COUNT] = {0, 1, 2, 3, 4, 5, 6, 7};
-  BlockTally<QB_TSTAT_COUNT>::publish(T.tally, reinterpret_cast<u64*>(A.stats), slot);
-}
-
-// The grid's cap: the workgroups the device holds at once (occupancy x CUs),
-// so every workgroup strides the same number of tiles and none waits for a
-// slot; kTickBlocks if the runtime will not say.  Asked once per process.
-inline unsigned resident_blocks() {
-  static const unsigned n = [] {
-    int dev = 0, per_cu = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_tick, kBlock, 0) != hipSuccess ||
-        per_cu <= 0 || cus <= 0) {
-      (void)hipGetLastError();
-      return kTickBlocks;
-    }
-    const unsigned r = unsigned(per_cu) * unsigned(cus);
-    return r < kTickBlocks ? r : kTickBlocks;
-  }();
-  return n;
+  BlockTally<QB_TSTAT_COUNT>::publish(T.tally, reinterpret_cast<u64*>(A.stats));
 }
 
 }  // namespace tick
@@ -336,8 +305,7 @@ extern "C" int qb_dev_leader_tick(const qb_tick_groups* tg, uint8_t* tflags, uin
              tg->readq_cap);
   tick::Args A{*tg, tflags, reinterpret_cast<u64*>(hb_commit), reinterpret_cast<u64*>(hb_ctx),
                reinterpret_cast<u64*>(stats)};
-  const unsigned tiles = grid_for(tg->G), cap = tick::resident_blocks();
-  hipLaunchKernelGGL(tick::k_tick, dim3(tiles < cap ? tiles : cap), dim3(kBlock), 0,
+  hipLaunchKernelGGL(tick::k_tick, dim3(stream_grid<tick::k_tick>(tg->G)), dim3(kBlock), 0,
                      as_stream(stream), A);
   QB_CHECK_LAUNCH("k_tick");
   return QB_OK;
