@@ -18,12 +18,15 @@ import torch
 
 from . import batch
 from .batch import INDEX_INF
-# (campaign the function takes the submodule's name here, as the call is named
-# in the header; the submodule stays importable as etcd_amd.quorum.campaign)
+# (campaign and ready the functions take their submodules' names here, as the
+# calls are named in the header; the submodules stay importable as
+# etcd_amd.quorum.campaign and etcd_amd.quorum.ready)
 from .campaign import CampaignResult, ElectionState, campaign
 from .follower import (FollowerAppInbox, FollowerGroups, FollowerInbox, FollowerLog,
                        FollowerLogResult, FollowerResult, follower_log_step, follower_step)
 from .propose import ProposeInbox, ProposeResult, ProposeState, leader_propose
+from .ready import (AdvanceRecords, AdvanceResult, ReadyResult, ReadyState, advance, ready,
+                    unstable_truncate)
 from .request import RequestInbox, RequestResult, leader_requests
 from .tick import TickResult, TickState, leader_tick
 
@@ -180,7 +183,7 @@ def vote_results(configs: Sequence[JointConfig], votes: Sequence[Mapping[int, bo
     return [VoteResult(int(x)) for x in out]
 
 
-__all__ = ["AckedIndexer", "CampaignResult", "ElectionState", "FollowerAppInbox", "FollowerGroups", "FollowerInbox", "FollowerLog", "FollowerLogResult", "FollowerResult", "INDEX_INF",
-           "JointConfig", "MAX_UINT64", "MajorityConfig", "MapAckIndexer", "ProposeInbox", "ProposeResult", "ProposeState", "RequestInbox", "RequestResult", "TickResult",
-           "TickState", "VoteLost", "VotePending", "VoteResult", "VoteWon", "batch", "campaign", "committed_indexes", "follower_log_step", "follower_step", "index_string", "leader_propose", "leader_requests", "leader_tick",
-           "vote_results"]
+__all__ = ["AckedIndexer", "AdvanceRecords", "AdvanceResult", "CampaignResult", "ElectionState", "FollowerAppInbox", "FollowerGroups", "FollowerInbox", "FollowerLog", "FollowerLogResult", "FollowerResult", "INDEX_INF",
+           "JointConfig", "MAX_UINT64", "MajorityConfig", "MapAckIndexer", "ProposeInbox", "ProposeResult", "ProposeState", "ReadyResult", "ReadyState", "RequestInbox", "RequestResult", "TickResult",
+           "TickState", "VoteLost", "VotePending", "VoteResult", "VoteWon", "advance", "batch", "campaign", "committed_indexes", "follower_log_step", "follower_step", "index_string", "leader_propose", "leader_requests", "leader_tick",
+           "ready", "unstable_truncate", "vote_results"]

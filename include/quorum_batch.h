@@ -1520,6 +1520,252 @@ int qb_dev_leader_requests(const qb_request_groups* rg, const qb_request_in* in,
                            const qb_request_out* out, uint64_t* stats, void* stream);
 
 /* ----------------------------------------------------------------------- */
+/* Ready and Advance: which groups have work, and what the host finished   */
+/* ----------------------------------------------------------------------- */
+
+/* RawNode.HasReady / readyWithoutAccept / acceptReady / Advance
+ * (rawnode.go:125-179) for G groups: after the step calls, qb_dev_ready finds
+ * the groups with work and lists them densely, so the host copies back R
+ * records instead of scanning G groups; after its I/O, qb_dev_advance takes R
+ * records back.  The entries' bytes, the messages and the ReadStates stay
+ * where the step calls left them; these calls move cursors.
+ *
+ * STATE.  Beside the step calls' own arrays (read only here), per group:
+ *   applied             raftLog.applied;
+ *   unstable_offset     unstable.offset: the unstable entries are
+ *                       [unstable_offset, last_index] (log_unstable.go:23-36);
+ *   usnap_index / usnap_term  the pending unstable.snapshot, index 0 = none
+ *                       (restore, which sets it, stays the host's);
+ *   prev_term / prev_vote / prev_commit   RawNode.prevHardSt;
+ *   prev_lead / prev_role                 RawNode.prevSoftSt (the role without
+ *                       QB_ROLE_PROMOTABLE).  NewRawNode starts both prevs at
+ *                       the current state (rawnode.go:52-53);
+ *   pending             QB_RDP_MSGS: len(r.msgs) > 0, QB_RDP_READSTATES:
+ *                       len(r.readStates) != 0.  The host sets the bits from
+ *                       the step calls' outputs;
+ *   uncommitted_size    qb_propose_groups::uncommitted_size.
+ *
+ * qb_dev_ready, per group, in newReady's terms (node.go:564-584):
+ *   QB_RDF_SOFT        lead != prev_lead, or role without QB_ROLE_PROMOTABLE
+ *                      != prev_role (SoftState.equal, node.go:45-47).
+ *   QB_RDF_HARD        (term, vote, committed) is not all zero and differs
+ *                      from (prev_term, prev_vote, prev_commit): HasReady's
+ *                      rule (rawnode.go:150-152).  newReady sets rd.HardState
+ *                      whenever it differs (node.go:573-575) and
+ *                      containsUpdates then asks !IsEmptyHardState
+ *                      (node.go:106-110): the same answer.
+ *   QB_RDF_ENTRIES     unstable_offset <= last_index (unstableEntries,
+ *                      log.go:173-178): the entries [unstable_offset,
+ *                      last_index], the last one's term last_term.
+ *   QB_RDF_SNAPSHOT    usnap_index != 0 (hasPendingSnapshot, log.go:203-205).
+ *   QB_RDF_COMMITTED   off = max(applied + 1, first_index) and committed + 1 >
+ *                      off (hasNextEnts / nextEnts, log.go:183-201): the range
+ *                      [off, committed], not paginated — maxNextEntsSize needs
+ *                      the entries' bytes, so the host trims the range and
+ *                      reports the cursor it reached to qb_dev_advance.
+ *   QB_RDF_MSGS, QB_RDF_READSTATES   copied from pending.
+ *   QB_RDF_MUST_SYNC   MustSync (node.go:589-595): QB_RDF_ENTRIES, or vote !=
+ *                      prev_vote, or term != prev_term.
+ *   QB_RDF_BAD_LOG     a state Go panics on or cannot reach: committed >
+ *                      last_index with something to apply (slice's bound,
+ *                      log.go:384-397), or unstable_offset > last_index + 1.
+ *                      The group carries this flag alone, is listed, and
+ *                      nothing of it is accepted.
+ * Index arithmetic wraps as Go's uint64 does.  rflags[g] is written for every
+ * group; a group is ready iff a bit other than QB_RDF_MUST_SYNC is set
+ * (containsUpdates).
+ *
+ * The ready groups are listed in ascending group order: record p of the list
+ * (p < min(*ready_count, ready_cap)) is written in every column —
+ *   ready_gid, rd_flags           the group and its rflags;
+ *   hs_term, hs_vote, hs_commit   the HardState with QB_RDF_HARD, else 0, 0, 0;
+ *   ent_lo, ent_hi, ent_last_term with QB_RDF_ENTRIES, else 0, 0, 0;
+ *   apply_lo, apply_hi            with QB_RDF_COMMITTED, else 0, 0;
+ *   snap_index                    usnap_index with QB_RDF_SNAPSHOT, else 0;
+ *   lead, role                    the SoftState (role without
+ *                                 QB_ROLE_PROMOTABLE), always
+ * — and no record at or past that count is touched.  *ready_count (device)
+ * gets the number of ready groups, listed or not.  A ready group whose
+ * position is >= ready_cap is deferred: rflags[g] |= QB_RDF_DEFERRED, no
+ * record, nothing accepted; the next call finds it again.
+ *
+ * accept != 0 runs acceptReady (rawnode.go:139-147) on every listed group
+ * without QB_RDF_BAD_LOG: with QB_RDF_SOFT prev_lead := lead and prev_role :=
+ * role without QB_ROLE_PROMOTABLE; pending[g] := 0.  No other state is
+ * written.  accept == 0 is HasReady + readyWithoutAccept: no state array is
+ * written at all. */
+#define QB_RDF_SOFT 0x0001u
+#define QB_RDF_HARD 0x0002u
+#define QB_RDF_ENTRIES 0x0004u
+#define QB_RDF_SNAPSHOT 0x0008u
+#define QB_RDF_COMMITTED 0x0010u
+#define QB_RDF_MSGS 0x0020u
+#define QB_RDF_READSTATES 0x0040u
+#define QB_RDF_MUST_SYNC 0x0080u
+#define QB_RDF_BAD_LOG 0x0100u
+#define QB_RDF_DEFERRED 0x0200u
+
+#define QB_RDP_MSGS 0x01u
+#define QB_RDP_READSTATES 0x02u
+
+#define QB_READY_MAX_GROUPS 0xFFFFFFFEull /* ready_gid is a uint32 */
+
+enum {
+  QB_RSTAT_SOFT = 0,        /* groups by flag, over all G groups */
+  QB_RSTAT_HARD = 1,
+  QB_RSTAT_ENTRIES = 2,
+  QB_RSTAT_SNAPSHOT = 3,
+  QB_RSTAT_COMMITTED = 4,
+  QB_RSTAT_MSGS = 5,
+  QB_RSTAT_READSTATES = 6,
+  QB_RSTAT_MUST_SYNC = 7,
+  QB_RSTAT_BAD_LOG = 8,
+  QB_RSTAT_DEFERRED = 9,    /* ready groups past ready_cap */
+  QB_RSTAT_LISTED = 10,     /* records written             */
+  QB_RSTAT_COUNT = 11
+};
+
+/* term .. pending_conf_index are the step calls' buffers (same layouts: a
+ * caller passes the same pointers) and are only read. */
+typedef struct qb_ready_groups {
+  uint64_t G;                         /* <= QB_READY_MAX_GROUPS */
+  const uint64_t* term;               /* [G] */
+  const uint64_t* vote;               /* [G] */
+  const uint64_t* committed;          /* [G] */
+  const uint64_t* lead;               /* [G] */
+  const uint8_t* role;                /* [G] QB_ROLE_* */
+  const uint64_t* first_index;        /* [G] */
+  const uint64_t* last_index;         /* [G] */
+  const uint64_t* last_term;          /* [G] */
+  const uint32_t* meta;               /* [G] bits 16-19: term runs (advance) */
+  const uint64_t* run_start;          /* [QB_LEADER_MAX_RUNS * G] run-major (advance) */
+  const uint64_t* run_term;           /* same layout */
+  const uint64_t* pending_conf_index; /* [G] (advance) */
+  const uint32_t* ext;                /* [G] nullable; bit 16: AutoLeave, as qb_dev_conf_change (advance) */
+  uint64_t* applied;                  /* [G] in/out: advance */
+  uint64_t* unstable_offset;          /* [G] in/out: advance, qb_dev_unstable_truncate */
+  uint64_t* usnap_index;              /* [G] in/out: advance */
+  uint64_t* usnap_term;               /* [G] in/out: advance */
+  uint64_t* prev_term;                /* [G] in/out: advance */
+  uint64_t* prev_vote;                /* [G] in/out: advance */
+  uint64_t* prev_commit;              /* [G] in/out: advance */
+  uint64_t* prev_lead;                /* [G] in/out: ready with accept */
+  uint8_t* prev_role;                 /* [G] in/out: ready with accept */
+  uint8_t* pending;                   /* [G] in/out: QB_RDP_*; ready with accept */
+  uint64_t* uncommitted_size;         /* [G] in/out: advance */
+} qb_ready_groups;
+
+typedef struct qb_ready_out {
+  uint16_t* rflags;        /* [G] QB_RDF_*, written for every group */
+  /* the list, [ready_cap] each */
+  uint32_t* ready_gid;
+  uint16_t* rd_flags;
+  uint64_t* hs_term;
+  uint64_t* hs_vote;
+  uint64_t* hs_commit;
+  uint64_t* ent_lo;
+  uint64_t* ent_hi;
+  uint64_t* ent_last_term;
+  uint64_t* apply_lo;
+  uint64_t* apply_hi;
+  uint64_t* snap_index;
+  uint64_t* lead;
+  uint8_t* role;
+  uint64_t* ready_count;   /* device, one */
+} qb_ready_out;
+
+/* stats: QB_RSTAT_COUNT device uint64 (accumulated).  Every pointer but ext
+ * is required (the list's columns too with ready_cap == 0: pass any valid
+ * pointer); run_start, run_term, meta, pending_conf_index and
+ * uncommitted_size are not read by qb_dev_ready.  G == 0 is QB_OK and sets
+ * *ready_count = 0; G > QB_READY_MAX_GROUPS or a workspace below
+ * qb_ready_scratch_bytes(G) is QB_EINVAL.  No allocation inside the call
+ * (it can be graph-captured); nothing outside the caller's arrays is read or
+ * written, whatever they hold. */
+size_t qb_ready_scratch_bytes(uint64_t G);
+int qb_dev_ready(const qb_ready_groups* rg, int accept, uint64_t ready_cap,
+                 const qb_ready_out* out, uint64_t* stats, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
+/* RawNode.Advance (rawnode.go:172-179) -> raft.advance (raft.go:543-580) for
+ * the A groups the host finished, one dense record each.  adv_gid values are
+ * distinct (two records of one group race); the Ready list's ascending order
+ * is the fast case and is not required.  A record whose adv_gid >= G gets
+ * QB_AFLAG_BAD_GROUP and is dropped.  Per record, in Go's order:
+ *   0. appliedTo's panic (log.go:246-254), found before anything of the
+ *      record is applied: applied_to != 0 and (committed < applied_to or
+ *      applied_to < applied) is QB_AFLAG_APPLIED_RANGE and nothing below runs.
+ *   1. (hs_term, hs_vote, hs_commit) not all zero: prev_term / prev_vote /
+ *      prev_commit := it (rawnode.go:174-177).  The host passes the Ready's
+ *      hs_* columns back.
+ *   2. reduceUncommittedSize (raft.go:1783-1801) by applied_payload, the sum
+ *      of PayloadSize over the entries handed to the application: nothing at
+ *      uncommitted_size == 0, else uncommitted_size -= applied_payload,
+ *      saturating at 0.
+ *   3. applied_to != 0 (appliedCursor, node.go:112-123: the last index handed
+ *      to the application — apply_hi, or less after the host paginated — or
+ *      the snapshot's index): applied := applied_to.  With AutoLeave (ext bit
+ *      16), oldApplied <= pending_conf_index <= applied_to and a leader's
+ *      role: QB_AFLAG_AUTO_LEAVE — the empty ConfChangeV2 append and the new
+ *      pending_conf_index stay the host's.
+ *   4. stable_index != 0: stableTo(stable_index, stable_term) (log.go:256,
+ *      log_unstable.go:77-89) against the log as it is now — it may have been
+ *      truncated since the Ready.  unstable_offset := stable_index + 1 iff
+ *      unstable_offset <= stable_index <= last_index and the term of
+ *      stable_index (last_term at last_index, else the run table, 0 below
+ *      first_index - 1) equals stable_term; else QB_AFLAG_STABLE_STALE and
+ *      the offset stays: the next Ready lists the entries again.
+ *   5. stable_snap != 0: stableSnapTo (log_unstable.go:109-113): usnap_index
+ *      := 0 and usnap_term := 0 iff usnap_index == stable_snap.
+ * aflags[i] is written for every record; nothing else is written but the
+ * state named above. */
+#define QB_AFLAG_APPLIED_RANGE 0x01u /* appliedTo would panic: nothing applied */
+#define QB_AFLAG_AUTO_LEAVE 0x02u    /* the host proposes the empty ConfChangeV2 */
+#define QB_AFLAG_STABLE_STALE 0x04u  /* stableTo matched nothing */
+#define QB_AFLAG_BAD_GROUP 0x08u     /* adv_gid >= G: dropped */
+
+enum {
+  QB_ASTAT_HARDSTATE = 0,     /* prevHardSt replaced            */
+  QB_ASTAT_APPLIED = 1,       /* applied moved (or re-set)      */
+  QB_ASTAT_AUTO_LEAVE = 2,
+  QB_ASTAT_STABLE = 3,        /* unstable_offset moved          */
+  QB_ASTAT_STABLE_STALE = 4,
+  QB_ASTAT_SNAP_STABLE = 5,   /* the pending snapshot cleared   */
+  QB_ASTAT_APPLIED_RANGE = 6,
+  QB_ASTAT_BAD_GROUP = 7,
+  QB_ASTAT_COUNT = 8
+};
+
+typedef struct qb_advance_in {  /* all [A] */
+  const uint32_t* adv_gid;
+  const uint64_t* hs_term;         /* all three 0: an empty HardState */
+  const uint64_t* hs_vote;
+  const uint64_t* hs_commit;
+  const uint64_t* applied_to;      /* 0 = none */
+  const uint64_t* applied_payload;
+  const uint64_t* stable_index;    /* 0 = none */
+  const uint64_t* stable_term;
+  const uint64_t* stable_snap;     /* 0 = none */
+} qb_advance_in;
+
+/* stats: QB_ASTAT_COUNT device uint64 (accumulated).  A == 0 is QB_OK and
+ * writes nothing; every pointer of rg but ext is required.  No workspace, no
+ * allocation (it can be graph-captured). */
+int qb_dev_advance(const qb_ready_groups* rg, uint64_t A, const qb_advance_in* in,
+                   uint8_t* aflags, uint64_t* stats, void* stream);
+
+/* What qb_dev_follower_log_step leaves to the host for unstable_offset:
+ * unstable.truncateAndAppend (log_unstable.go:121-145) sets, in each of its
+ * three cases, offset := min(offset, index of the first appended entry).
+ * For every record i < M with app_from[i] != 0 and group[i] < G:
+ * unstable_offset[group[i]] := min(unstable_offset[group[i]], app_from[i]), a
+ * 64-bit atomic min, so the records' order does not matter.  group and
+ * app_from are the log step's rec_group column and app_from output.  M == 0
+ * is QB_OK. */
+int qb_dev_unstable_truncate(uint64_t M, const uint32_t* group, const uint64_t* app_from,
+                             uint64_t G, uint64_t* unstable_offset, void* stream);
+
+/* ----------------------------------------------------------------------- */
 /* Wire ingest                                       */
 /* ----------------------------------------------------------------------- */
 

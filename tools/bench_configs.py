@@ -1951,6 +1951,228 @@ def requests_config(G, reps, *, reporter=None):
     assert ok, "requests parity failed"
 
 
+def ready_config(G, reps, *, reporter=None):
+    """Ready + Advance (qb_dev_ready, qb_dev_advance) over G five-voter leader
+    groups of the synth_streaming table.  Two samples: 1 % of the groups ready
+    (every 100th) and all of them; a ready group has one unstable entry, one
+    committed entry to apply, a HardState whose commit moved and messages
+    pending.  A sample is one accepting qb_dev_ready with room for every group
+    and one qb_dev_advance over the list it wrote, the list's columns handed
+    back as they are (the host's I/O between the two is not modelled), behind
+    which every group is idle again.  HIP events before, between and behind
+    the two calls, median over the samples after warm-up; the eleven state
+    columns are put back between samples outside the timed calls; calls
+    straight to the C ABI.  Parity: one more Ready and Advance at the same size
+    over seeded state — the flags and the compaction of all G groups against
+    numpy, every 1024th group against tests/ready_ref.py."""
+    reporter = reporter or report
+    import ctypes as C
+    import importlib
+    import time
+    from etcd_amd import _lib
+    from etcd_amd.quorum import tick as qt
+    from etcd_amd.quorum.leader import MAX_RUNS, synth_streaming
+    from tests import ready_pack as P, ready_ref as R
+    qc = importlib.import_module("etcd_amd.quorum.campaign")
+    qy = importlib.import_module("etcd_amd.quorum.ready")
+    n = 5
+    lg, _ = synth_streaming(G, W=4, D=64, n=n, device=dev)
+    z32 = lambda: torch.zeros(G, dtype=torch.int32, device=dev)  # noqa: E731
+    z64 = lambda: torch.zeros(G, dtype=torch.int64, device=dev)  # noqa: E731
+    tstate = qt.TickState(torch.full((G,), qt.ROLE_LEADER | qt.ROLE_PROMOTABLE, dtype=torch.uint8,
+                                     device=dev), z32(), z32(), z32())
+    es = qc.ElectionState.for_table(lg, tstate, np.arange(1, G + 1, dtype=np.uint64),
+                                    np.ones(G, np.uint64), np.ones(G, np.uint64),
+                                    np.full(G, 7, np.uint64), 10, True, True)
+    ft, t = es.follower.t, lg.t
+    shared = {"term": ft["term"], "vote": ft["vote"], "committed": ft["committed"],
+              "lead": ft["lead"], "role": tstate.role, "first_index": t["first_index"],
+              "last_index": ft["last_index"], "last_term": ft["last_term"], "meta": t["meta"],
+              "run_start": t["run_start"], "run_term": t["run_term"], "pending_conf_index": z64(),
+              "ext": z32()}
+    st = qy.ReadyState.new_raw_node(shared, ft["committed"].clone(), z64())
+    s = st.t
+    idle = {k: s[k].clone() for k in P.STATE}
+    out = qy.new_ready_result(G, G, dev)
+    pay = torch.full((G,), 8, dtype=torch.int64, device=dev)
+    recs = qy.AdvanceRecords(G, {"adv_gid": out.cols["ready_gid"], "hs_term": out.cols["hs_term"],
+                                 "hs_vote": out.cols["hs_vote"], "hs_commit": out.cols["hs_commit"],
+                                 "applied_to": out.cols["apply_hi"], "applied_payload": pay,
+                                 "stable_index": out.cols["ent_hi"],
+                                 "stable_term": out.cols["ent_last_term"],
+                                 "stable_snap": out.cols["snap_index"]})
+    ares = qy.AdvanceResult(torch.zeros(G, dtype=torch.uint8, device=dev),
+                            torch.zeros(len(qy.ASTAT_NAMES), dtype=torch.int64, device=dev))
+    qy.ready(st, accept=False, out=out)       # (the mirror's checks and the workspace, once)
+    qy.advance(st, qy.AdvanceRecords(0, recs.t), out=ares)
+    out.stats.zero_()
+    rg = st.struct()
+    ro = qy.ReadyOutC(rflags=out.rflags.data_ptr(), ready_count=out.ready_count.data_ptr(),
+                      **{k: out.cols[k].data_ptr() for k in qy._LIST})
+    ai = qy.AdvanceInC(**{k: recs.t[k].data_ptr() for k in qy._ADV})
+    sp = torch.cuda.current_stream(dev).cuda_stream
+    f_ready, f_adv = _lib.fn("qb_dev_ready"), _lib.fn("qb_dev_advance")
+    ws = st._ws
+
+    def call_ready(accept, cap):
+        _lib.check(f_ready(C.byref(rg), accept, cap, C.byref(ro), out.stats.data_ptr(),
+                           ws.data_ptr(), ws.numel(), sp), "qb_dev_ready")
+
+    def call_advance(A):
+        _lib.check(f_adv(C.byref(rg), A, C.byref(ai), ares.aflags.data_ptr(),
+                         ares.stats.data_ptr(), sp), "qb_dev_advance")
+
+    def timed(every):
+        g = torch.arange(G, device=dev)
+        on = g % every == 0
+        Rn = int(on.sum().item())
+        work = {k: v.clone() for k, v in idle.items()}
+        work["unstable_offset"] = torch.where(on, ft["last_index"], idle["unstable_offset"])
+        work["applied"] = torch.where(on, ft["committed"] - 1, idle["applied"])
+        work["prev_commit"] = torch.where(on, ft["committed"] - 1, idle["prev_commit"])
+        work["pending"] = on.to(torch.uint8) * qy.RDP_MSGS
+        work["uncommitted_size"] = on.to(torch.int64) * 16
+
+        def sample(ev):
+            for k, v in work.items():
+                s[k].copy_(v)
+            torch.cuda.synchronize()
+            ev.record(ev.ev[0], sp)
+            call_ready(1, G)
+            ev.record(ev.ev[1], sp)
+            call_advance(Rn)
+            ev.record(ev.ev[2], sp)
+            torch.cuda.synchronize()
+            return ev.elapsed_ms(0, 1) / 1e3, ev.elapsed_ms(1, 2) / 1e3
+        ev = HipEvents(3)
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < 0.3:  # warm-up: clocks settle (time_region)
+            sample(ev)
+        out.stats.zero_()
+        ares.stats.zero_()
+        per = [sample(ev) for _ in range(reps)]
+        ev.close()
+        rs, as_ = out.stats_dict(), ares.stats_dict()
+        assert int(out.ready_count.cpu()[0]) == Rn and rs["listed"] == reps * Rn, rs
+        assert rs["entries"] == rs["committed"] == rs["hard"] == rs["msgs"] == reps * Rn, rs
+        assert as_["stable"] == as_["applied"] == as_["hardstate"] == reps * Rn, as_
+        assert all(bool((s[k] == idle[k]).all()) for k in P.STATE if k != "uncommitted_size")
+        call_ready(0, G)                       # behind the Advance nothing is ready
+        assert int(out.ready_count.cpu()[0]) == 0
+        return (float(np.median([a for a, _ in per])), float(np.median([b for _, b in per])), Rn)
+
+    # Bytes per group, the columns each launch touches (not a traffic counter).
+    # R1: 13 u64 columns + role, prev_role, pending read, rflags written.
+    r1_b = 13 * 8 + 3 + 2
+    # R2: rflags read per group; per listed group of these samples lead 8, role
+    # 1, committed 8, applied 8, first_index 8, term 8, vote 8, unstable_offset
+    # 8, last_index 8, last_term 8 read, the record (4 + 2 + 10 * 8 + 1)
+    # and pending written.
+    r2_b, r2_rec = 2, 73 + 87 + 1
+    # Advance, per record: the nine columns 68 read, aflags 1 written; applied,
+    # committed, uncommitted_size, unstable_offset, last_index, last_term read
+    # 48; prev_* 24, applied 8, uncommitted_size 8, unstable_offset 8 written.
+    adv_rec = 68 + 1 + 48 + 48
+    rows = {}
+    for name, every in (("all", 1), ("one_percent", 100)):
+        t_r, t_a, Rn = timed(every)
+        b = G * (r1_b + r2_b) + Rn * (r2_rec + adv_rec)
+        rows[name] = {"ready_groups": Rn, "ready_us": t_r * 1e6, "advance_us": t_a * 1e6,
+                      "ready_advance_us": (t_r + t_a) * 1e6, "bytes": b,
+                      "TBs": b / (t_r + t_a) / 1e12,
+                      "frac": b / (t_r + t_a) / 1e9 / HBM_PEAK_GBS}
+    extra = {"unit": "groups/s", "samples": reps,
+             "bytes_per_group": {"k_ready_flags": r1_b, "k_ready_write": r2_b,
+                                 "k_ready_write_per_listed": r2_rec, "k_advance_per_record": adv_rec},
+             "timing": "HIP events before, between and behind qb_dev_ready and qb_dev_advance, "
+                       "median over the samples; per_launch_us = ready + advance, every group "
+                       "ready", **{f"{k}_{f}": v for k, r in rows.items() for f, v in r.items()}}
+
+    # ---- parity at this size over seeded state ---------------------------
+    gen = torch.Generator(device=dev).manual_seed(0x4EAD7)
+    rnd = lambda hi: torch.randint(0, hi, (G,), generator=gen, device=dev)  # noqa: E731
+    for k, v in idle.items():
+        s[k].copy_(v)
+    act = rnd(4) == 0
+    w = lambda a, b: torch.where(act, a, b)  # noqa: E731
+    last, com = ft["last_index"], ft["committed"]
+    s["applied"].copy_(w(com - rnd(3), idle["applied"]))
+    s["unstable_offset"].copy_(w(torch.where(rnd(64) == 0, last + 3, last + 1 - rnd(3)),
+                                 idle["unstable_offset"]))
+    s["prev_commit"].copy_(w(com - rnd(2), idle["prev_commit"]))
+    s["prev_term"].copy_(w(ft["term"] - (rnd(16) == 0).long(), idle["prev_term"]))
+    s["prev_lead"].copy_(w(ft["lead"] + (rnd(8) == 0).long(), idle["prev_lead"]))
+    s["prev_role"].copy_(w(torch.where(rnd(8) == 0, 1, 2), z64() + 2).to(torch.uint8))
+    s["pending"].copy_(w(torch.where(rnd(4) == 0, rnd(4), z64()), z64()).to(torch.uint8))
+    s["usnap_index"].copy_(w(torch.where(rnd(32) == 0, 5 + rnd(3), z64()), idle["usnap_index"]))
+    s["usnap_term"].copy_(torch.where(s["usnap_index"] != 0, 7, 0))
+    s["uncommitted_size"].copy_(w(rnd(3) * 8, idle["uncommitted_size"]))
+    st.t["ext"].copy_((rnd(16) == 0).to(torch.int32) << 16)     # AutoLeave, the change pending
+    st.t["pending_conf_index"].copy_(com)                       # at the commit index
+    sub = np.arange(0, G, 1024)
+    rows_ = (np.arange(MAX_RUNS)[:, None] * G + sub[None, :]).ravel()
+
+    def gather():
+        a = st.numpy()
+        return {k: (v[rows_] if k.startswith("run_") else v[sub]).copy() for k, v in a.items()}
+    nodes = P.nodes_from_arrays(gather())
+    call_ready(0, G)
+    count = int(out.ready_count.cpu()[0])
+    cap = count - 5
+    for c_ in out.cols.values():
+        c_.fill_(255 if c_.dtype == torch.uint8 else -1)
+    out.stats.zero_()
+    ares.stats.zero_()
+    call_ready(1, cap)
+    call_advance(cap)
+    torch.cuda.synchronize()
+    rf = out.rflags.cpu().numpy().view(np.uint16)[:G]
+    rdy = np.flatnonzero(rf & ~np.uint16(R.RDF_MUST_SYNC | R.RDF_DEFERRED))
+    cols = {k: out.cols[k].cpu().numpy().view(dt) for k, dt in P.LIST.items()}
+    ok = (len(rdy) == count == int(out.ready_count.cpu()[0])
+          and np.array_equal(cols["ready_gid"][:cap], rdy[:cap].astype(np.uint32))
+          and np.array_equal(cols["rd_flags"][:cap], rf[rdy[:cap]])
+          and bool((cols["ready_gid"][cap:] == 0xFFFFFFFF).all())
+          and np.array_equal(np.flatnonzero(rf & R.RDF_DEFERRED), rdy[cap:]))
+    # every 1024th group against the restatement: its flags, its record, its
+    # Advance (groups are independent but for the list position and the cap)
+    pos = np.searchsorted(rdy, sub)
+    recs_ref = []
+    for i, (g, nd) in enumerate(zip(sub, nodes)):
+        f, rd = R.ready_flags(nd)
+        listed = bool(f & ~R.RDF_MUST_SYNC) and pos[i] < cap
+        if f & ~R.RDF_MUST_SYNC and not listed:
+            f |= R.RDF_DEFERRED
+        ok = ok and int(rf[g]) == f
+        if not listed:
+            continue
+        _, rr, _, _ = R.ready_call([nd], True, 1)
+        r = rr[0]
+        p = int(pos[i])
+        got = tuple(int(cols[k][p]) for k in ("hs_term", "hs_vote", "hs_commit", "ent_lo", "ent_hi",
+                                              "ent_last_term", "apply_lo", "apply_hi", "snap_index",
+                                              "lead", "role"))
+        ok = ok and got == r.hs + r.ent + r.apply + (r.snap_index, r.lead, r.role)
+        fl = R.advance(nd, R.AdvanceRecord(0, r.hs, r.apply[1], 8, r.ent[1], r.ent[2],
+                                           r.snap_index))
+        ok = ok and int(ares.aflags[p].item()) == fl
+    want = P.pack_nodes(nodes)
+    got = gather()
+    ok = ok and all(np.array_equal(got[k], want[k]) for k in P.STATE)
+    rs, as_ = out.stats_dict(), ares.stats_dict()
+    ok = ok and all(v > 0 for v in rs.values()) and rs["listed"] == cap and rs["deferred"] == 5
+    ok = ok and all(as_[k] > 0 for k in ("hardstate", "applied", "stable", "snap_stable",
+                                         "auto_leave"))
+    extra["parity"] = bool(ok)
+    extra["parity_check"] = (f"all {G} groups' flags compacted against numpy ({count} ready, the "
+                             f"last 5 deferred); tests/ready_ref.py over {len(sub)} groups (every "
+                             f"1024th): rflags, the record, aflags and the eleven state columns "
+                             f"behind Ready + Advance; stats: {rs} {as_}")
+    reporter("ready + advance (every group ready: one entry to persist, one to apply)", G,
+             (rows["all"]["ready_us"] + rows["all"]["advance_us"]) / 1e6, rows["all"]["bytes"], extra)
+    assert ok, "ready parity failed"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -2000,6 +2222,8 @@ def main():
         propose_config(1 << 22, a.reps)
     if "requests" in which:
         requests_config(1 << 22, a.reps)
+    if "ready" in which:
+        ready_config(1 << 22, a.reps)
     if "wire-tracker" in which:
         wire_tracker_config(1 << 24, a.reps)
     if "wire-tracker-fused" in which:  # development A/B: the one call alone
