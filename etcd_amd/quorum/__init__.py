@@ -28,6 +28,7 @@ from .propose import ProposeInbox, ProposeResult, ProposeState, leader_propose
 from .ready import (AdvanceRecords, AdvanceResult, ReadyResult, ReadyState, advance, ready,
                     unstable_truncate)
 from .request import RequestInbox, RequestResult, leader_requests
+from .snapshot import SnapshotInbox, SnapshotResult, follower_snapshot, restored_conf_states
 from .tick import TickResult, TickState, leader_tick
 
 MAX_UINT64 = INDEX_INF
@@ -184,6 +185,6 @@ def vote_results(configs: Sequence[JointConfig], votes: Sequence[Mapping[int, bo
 
 
 __all__ = ["AckedIndexer", "AdvanceRecords", "AdvanceResult", "CampaignResult", "ElectionState", "FollowerAppInbox", "FollowerGroups", "FollowerInbox", "FollowerLog", "FollowerLogResult", "FollowerResult", "INDEX_INF",
-           "JointConfig", "MAX_UINT64", "MajorityConfig", "MapAckIndexer", "ProposeInbox", "ProposeResult", "ProposeState", "ReadyResult", "ReadyState", "RequestInbox", "RequestResult", "TickResult",
-           "TickState", "VoteLost", "VotePending", "VoteResult", "VoteWon", "advance", "batch", "campaign", "committed_indexes", "follower_log_step", "follower_step", "index_string", "leader_propose", "leader_requests", "leader_tick",
-           "ready", "unstable_truncate", "vote_results"]
+           "JointConfig", "MAX_UINT64", "MajorityConfig", "MapAckIndexer", "ProposeInbox", "ProposeResult", "ProposeState", "ReadyResult", "ReadyState", "RequestInbox", "RequestResult", "SnapshotInbox", "SnapshotResult", "TickResult",
+           "TickState", "VoteLost", "VotePending", "VoteResult", "VoteWon", "advance", "batch", "campaign", "committed_indexes", "follower_log_step", "follower_snapshot", "follower_step", "index_string", "leader_propose", "leader_requests", "leader_tick",
+           "ready", "restored_conf_states", "unstable_truncate", "vote_results"]

@@ -1535,7 +1535,7 @@ int qb_dev_leader_requests(const qb_request_groups* rg, const qb_request_in* in,
  *   unstable_offset     unstable.offset: the unstable entries are
  *                       [unstable_offset, last_index] (log_unstable.go:23-36);
  *   usnap_index / usnap_term  the pending unstable.snapshot, index 0 = none
- *                       (restore, which sets it, stays the host's);
+ *                       (qb_dev_follower_snapshot's restore sets it);
  *   prev_term / prev_vote / prev_commit   RawNode.prevHardSt;
  *   prev_lead / prev_role                 RawNode.prevSoftSt (the role without
  *                       QB_ROLE_PROMOTABLE).  NewRawNode starts both prevs at
@@ -1764,6 +1764,177 @@ int qb_dev_advance(const qb_ready_groups* rg, uint64_t A, const qb_advance_in* i
  * is QB_OK. */
 int qb_dev_unstable_truncate(uint64_t M, const uint32_t* group, const uint64_t* app_from,
                              uint64_t G, uint64_t* unstable_offset, void* stream);
+
+/* ----------------------------------------------------------------------- */
+/* Follower snapshot: MsgSnap, handleSnapshot, restore                     */
+/* ----------------------------------------------------------------------- */
+
+/* raft.Step (raft.go:847-984) for MsgSnap at nodes that are not leading, for
+ * R records in one call: the receiving side of the QB_MSG_SNAP that
+ * qb_dev_leader_step, qb_dev_leader_propose and qb_dev_leader_requests emit,
+ * and the writer of the unstable snapshot that qb_dev_ready lists
+ * (QB_RDF_SNAPSHOT) and qb_dev_advance clears (stableSnapTo).  A record is one
+ * MsgSnap; the records of one call name distinct groups, as qb_dev_advance's
+ * do (two records of one group race): a second snapshot for a group waits for
+ * the next call.  The snapshot's data stays the host's; the call decides what
+ * the node does with it, moves the log's cursors and writes the response.
+ *
+ * The arrays are the step calls' own (same layouts: a caller passes the same
+ * buffers): qb_follower_groups, qb_follower_log, self_id of
+ * qb_campaign_groups, and unstable_offset / usnap_index / usnap_term / pending
+ * of qb_ready_groups.  This is the one call that writes first_index.
+ *
+ * A record: from / term = Message.From / Message.Term, snap_index / snap_term
+ * = Snapshot.Metadata.Index / Term, and Snapshot.Metadata.ConfState as the IDs
+ * cs_id[cs_off[i] .. cs_off[i + 1]) with cs_set[k] naming the list that holds
+ * ID k (QB_CS_*; any other value is in no list).  Offsets above C read as C.
+ *
+ * Per record, in Go's order:
+ *   Bad group: group >= G is QB_SNF_BAD_GROUP; nothing else happens.
+ *   Term filter (raft.go:849-920), with Term != 0 (0 skips it, as for any
+ *     message with Term 0):
+ *     higher term: becomeFollower(m.Term, m.From) (raft.go:876-877) -> reset
+ *       (raft.go:686-693, 590-619), restricted to the fields this call owns,
+ *       exactly as qb_dev_follower_step states it: term (and vote := 0) change
+ *       only if the term differs, lead is set, both counters 0, role :=
+ *       Follower with the other bits of the byte kept, QB_SNF_RESET;
+ *     lower term: ignored whatever check_quorum / pre_vote say — those
+ *       branches name MsgApp, MsgHeartbeat and MsgPreVote only (raft.go:884,
+ *       907).  QB_SNF_STALE, no response, nothing written.
+ *   By role at or above the term: a leader ignores it (stepLeader has no case
+ *     for it): QB_SNF_ROLE_IGNORED, no response, nothing written.  A
+ *     (pre-)candidate runs becomeFollower(m.Term, m.From) (raft.go:1396-1398;
+ *     QB_SNF_RESET), a follower sets election_elapsed = 0 and lead = From
+ *     (raft.go:1441-1444).
+ *   handleSnapshot -> restore (raft.go:1518-1614):
+ *     1. snap_index <= committed (raft.go:1535-1537): QB_SNF_OLD,
+ *        MsgAppResp{Index: committed}.
+ *     2. self_id[g] is in none of Voters / Learners / VotersOutgoing
+ *        (raft.go:1554-1580; LearnersNext does not count): QB_SNF_NOT_MEMBER,
+ *        MsgAppResp{Index: committed}.
+ *     3. matchTerm(snap_index, snap_term) (raft.go:1584-1589, log.go:320-326),
+ *        the term of snap_index being last_term at last_index, the run
+ *        table's inside the log and 0 outside [first_index - 1, last_index]
+ *        (log.go:268-274): commitTo(snap_index), i.e. committed := snap_index;
+ *        QB_SNF_FAST_FORWARD, MsgAppResp{Index: committed}.
+ *     4. Else raftLog.restore + unstable.restore (log.go:336-340,
+ *        log_unstable.go:115-119): committed := snap_index, unstable_offset :=
+ *        snap_index + 1, usnap_index := snap_index, usnap_term := snap_term,
+ *        last_index := snap_index, last_term := snap_term, first_index :=
+ *        snap_index + 1 (maybeFirstIndex, log_unstable.go:35-40), the run
+ *        table one run (snap_index, snap_term) with the count in meta bits
+ *        16-19 set to 1 — rows 1..7 of the table keep what they hold — and
+ *        QB_ROLE_PROMOTABLE cleared: promotable() is false while a snapshot
+ *        is pending (raft.go:1618-1621; TestRestore: "It should not campaign
+ *        before actually applying data").  QB_SNF_RESTORED,
+ *        MsgAppResp{Index: last_index}.
+ *     The r.state != StateFollower branch of restore (raft.go:1538-1549) is
+ *     unreachable: both callers have made the node a follower.  It is not
+ *     modelled.
+ *   Stop, QB_SNF_COMMIT_RANGE: the one state Go panics on.  A record that
+ *     reaches step 3 with snap_index > last_index matches exactly when
+ *     snap_term == 0 (term() is 0 outside the log), and commitTo then panics
+ *     (log.go:239-241).  It is found before anything of the record is
+ *     applied, the term filter's effect included, as the log step's stops
+ *     are: this flag alone, no response, nothing written.
+ *   Response: resp_type = QB_FRESP_APP_RESP or 0 (none), resp_term = term[g]
+ *     behind the filter (as send stamps it), resp_index; To = from[i].  With
+ *     pending != NULL a record with a response ORs QB_RDP_MSGS into
+ *     pending[g].
+ *   QB_SNF_HARDSTATE: term, vote or committed differ from their values at
+ *     entry — what Ready persists before the response may be sent.
+ * Index arithmetic wraps as Go's uint64 does.
+ *
+ * What stays the host's behind QB_SNF_RESTORED: the
+ * ProgressTracker reset and confchange.Restore of the record's ConfState
+ * (raft.go:1593-1606: the qb_dev_conf_change sequence with LastIndex =
+ * snap_index), the own slot's MaybeUpdate(Next - 1) (raft.go:1608-1609), and
+ * setting QB_ROLE_PROMOTABLE again once the snapshot is stable and the config
+ * is in; behind QB_SNF_RESET the rest of reset, as for the follower step. */
+#define QB_CS_VOTERS 0          /* ConfState.Voters         */
+#define QB_CS_LEARNERS 1        /* ConfState.Learners       */
+#define QB_CS_VOTERS_OUTGOING 2 /* ConfState.VotersOutgoing */
+#define QB_CS_LEARNERS_NEXT 3   /* ConfState.LearnersNext   */
+
+#define QB_SNF_RESTORED 0x0001u     /* the log is the snapshot now             */
+#define QB_SNF_FAST_FORWARD 0x0002u /* the log held it: committed moved        */
+#define QB_SNF_OLD 0x0004u          /* snap_index <= committed                 */
+#define QB_SNF_NOT_MEMBER 0x0008u   /* the node is not in the ConfState        */
+#define QB_SNF_STALE 0x0010u        /* lower term: ignored                     */
+#define QB_SNF_ROLE_IGNORED 0x0020u /* a leader: ignored                       */
+#define QB_SNF_RESET 0x0040u        /* becomeFollower ran: the host's reset    */
+#define QB_SNF_COMMIT_RANGE 0x0080u /* stopped: commitTo would panic           */
+#define QB_SNF_BAD_GROUP 0x0100u    /* group >= G: dropped                     */
+#define QB_SNF_HARDSTATE 0x0200u    /* term / vote / committed changed         */
+
+enum {
+  QB_SSTAT_RESTORED = 0,        /* records by flag: the first nine bits */
+  QB_SSTAT_FAST_FORWARD = 1,
+  QB_SSTAT_OLD = 2,
+  QB_SSTAT_NOT_MEMBER = 3,
+  QB_SSTAT_STALE = 4,
+  QB_SSTAT_ROLE_IGNORED = 5,
+  QB_SSTAT_BECAME_FOLLOWER = 6, /* becomeFollower calls (QB_SNF_RESET)  */
+  QB_SSTAT_COMMIT_RANGE = 7,
+  QB_SSTAT_BAD_GROUP = 8,
+  QB_SSTAT_COUNT = 9
+};
+
+typedef struct qb_snapshot_groups {
+  uint64_t G;                   /* <= QB_READY_MAX_GROUPS                       */
+  uint32_t election_timeout;    /* as qb_follower_groups; not read by MsgSnap   */
+  uint32_t check_quorum;        /* same                                         */
+  uint32_t pre_vote;            /* same                                         */
+  uint32_t reserved;            /* 0                                            */
+  const uint64_t* self_id;      /* [G] the node's raft ID                       */
+  uint64_t* term;               /* [G] in/out */
+  uint64_t* vote;               /* [G] in/out */
+  uint64_t* lead;               /* [G] in/out */
+  uint64_t* committed;          /* [G] in/out */
+  uint8_t* role;                /* [G] in/out: QB_ROLE_*                        */
+  uint32_t* election_elapsed;   /* [G] in/out */
+  uint32_t* heartbeat_elapsed;  /* [G] in/out */
+  uint64_t* first_index;        /* [G] in/out */
+  uint64_t* last_index;         /* [G] in/out */
+  uint64_t* last_term;          /* [G] in/out */
+  uint32_t* meta;               /* [G] in/out: only bits 16-19 (term runs) may change */
+  uint64_t* run_start;          /* [QB_LEADER_MAX_RUNS * G] run-major, in/out: row 0 only */
+  uint64_t* run_term;           /* same layout */
+  uint64_t* unstable_offset;    /* [G] in/out */
+  uint64_t* usnap_index;        /* [G] in/out */
+  uint64_t* usnap_term;         /* [G] in/out */
+  uint8_t* pending;             /* [G] in/out: QB_RDP_*; nullable               */
+} qb_snapshot_groups;
+
+typedef struct qb_snapshot_inbox {
+  uint64_t R;                 /* <= 2^32 - 2                                    */
+  const uint32_t* group;      /* [R] distinct                                   */
+  const uint64_t* from;       /* [R] sender ID                                  */
+  const uint64_t* term;       /* [R] Message.Term; 0 skips the term filter      */
+  const uint64_t* snap_index; /* [R] Snapshot.Metadata.Index                    */
+  const uint64_t* snap_term;  /* [R] Snapshot.Metadata.Term                     */
+  const uint32_t* cs_off;     /* [R+1] record i's ConfState IDs: cs_off[i] ..
+                                 cs_off[i+1]; offsets above C read as C         */
+  const uint64_t* cs_id;      /* [C] the ConfState's IDs                        */
+  const uint8_t* cs_set;      /* [C] QB_CS_*: the list the ID is in             */
+  uint64_t C;
+} qb_snapshot_inbox;
+
+typedef struct qb_snapshot_out { /* all [R], written for every record */
+  uint16_t* sflags;     /* QB_SNF_*                                  */
+  uint8_t* resp_type;   /* 0 or QB_FRESP_APP_RESP                    */
+  uint64_t* resp_term;  /* Message.Term of the response (0 if none)  */
+  uint64_t* resp_index; /* Message.Index of the response (0 if none) */
+} qb_snapshot_out;
+
+/* stats: QB_SSTAT_COUNT device uint64 (accumulated).  R == 0 or G == 0 is
+ * QB_OK and writes nothing.  Every pointer but pending is required (cs_id and
+ * cs_set only with C > 0); a NULL struct, G > QB_READY_MAX_GROUPS or R > 2^32
+ * - 2 is QB_EINVAL.  No workspace and no allocation inside the call (it can be
+ * graph-captured); nothing outside the caller's arrays is read or written,
+ * whatever they hold. */
+int qb_dev_follower_snapshot(const qb_snapshot_groups* sg, const qb_snapshot_inbox* in,
+                             const qb_snapshot_out* out, uint64_t* stats, void* stream);
 
 /* ----------------------------------------------------------------------- */
 /* Wire ingest                                       */

@@ -2173,6 +2173,176 @@ def ready_config(G, reps, *, reporter=None):
     assert ok, "ready parity failed"
 
 
+def snapshot_config(G, reps, *, reporter=None):
+    """The batched MsgSnap step (qb_dev_follower_snapshot) over G follower
+    groups of the synth_streaming table (node 2 of five voters, leader 1
+    known, one term run).  Every record is a same-term MsgSnap from the leader
+    100 past the group's last index with a five-voter ConfState: it restores.
+    Row (a): a record for every group; row (b): for every 100th.  Records
+    arrive in shuffled group order, as the follower rows' do; (a) is also
+    timed in ascending order, the order qb_dev_advance's row has.  One HIP
+    event pair per call, median over the samples after warm-up; the eighteen
+    state columns are put back between samples outside the timed call; calls
+    straight to the C ABI.  Parity at this size: tests/snapshot_ref.py over
+    every 1024th group after one call of row (a) — sflags, the response and
+    every state column — and the whole batch's counters."""
+    reporter = reporter or report
+    import ctypes as C
+    import importlib
+    import time
+    from etcd_amd import _lib
+    from etcd_amd.quorum import follower as qf, snapshot as qs, tick as qt
+    from etcd_amd.quorum.leader import MAX_RUNS, synth_streaming
+    from tests import snapshot_pack as P, snapshot_ref as S
+    qy = importlib.import_module("etcd_amd.quorum.ready")
+    n, ET = 5, 10
+    lg, _ = synth_streaming(G, W=4, D=64, n=n, device=dev)
+    t = lg.t
+    i64 = lambda v: torch.full((G,), v, dtype=torch.int64, device=dev)  # noqa: E731
+    z32 = lambda: torch.zeros(G, dtype=torch.int32, device=dev)  # noqa: E731
+    tstate = qt.TickState(torch.full((G,), qt.ROLE_PROMOTABLE, dtype=torch.uint8, device=dev),
+                          torch.ones(G, dtype=torch.int32, device=dev), z32(), z32())
+    ft = {"term": t["term"], "vote": i64(1), "lead": i64(1), "committed": t["committed"],
+          "last_index": t["last_index"], "last_term": i64(7)}
+    fg = qf.FollowerGroups(G, ET, True, True, ft, tstate)
+    flog = qf.FollowerLog(G, t["meta"], t["first_index"], t["run_start"], t["run_term"])
+    ready = qy.ReadyState(G, {"unstable_offset": t["last_index"] + 1, "usnap_index": i64(0),
+                              "usnap_term": i64(0),
+                              "pending": torch.zeros(G, dtype=torch.uint8, device=dev)})
+    self_id = i64(2)
+    cols = {"self_id": self_id, **ft, "role": tstate.role,
+            "election_elapsed": tstate.election_elapsed,
+            "heartbeat_elapsed": tstate.heartbeat_elapsed, "first_index": t["first_index"],
+            "meta": t["meta"], "run_start": t["run_start"], "run_term": t["run_term"],
+            **ready.t}
+    assert set(cols) == set(P.STATE)
+    pristine = {k: v.clone() for k, v in cols.items()}
+    sp = torch.cuda.current_stream(dev).cuda_stream
+    fn = _lib.fn("qb_dev_follower_snapshot")
+
+    def inbox_of(groups):
+        """One restoring MsgSnap per group of ``groups`` (a device tensor)."""
+        Rn = int(groups.numel())
+        ids = torch.arange(1, n + 1, dtype=torch.int64, device=dev).repeat(Rn)
+        tt = {"group": groups.to(torch.int32), "from": torch.ones_like(groups),
+              "term": pristine["term"][groups], "snap_index": pristine["last_index"][groups] + 100,
+              "snap_term": torch.full_like(groups, 8),
+              "cs_off": (torch.arange(Rn + 1, dtype=torch.int64, device=dev) * n).to(torch.int32),
+              "cs_id": ids, "cs_set": torch.zeros(Rn * n, dtype=torch.uint8, device=dev)}
+        return qs.SnapshotInbox(Rn, Rn * n, tt)
+
+    def caller(ib, res):
+        qs.follower_snapshot(fg, flog, ready, self_id, ib, out=res, check_distinct=False)  # the checks, once
+        sg = qs.SnapshotGroupsC(G=G, election_timeout=ET, check_quorum=1, pre_vote=1, reserved=0,
+                                **{k: cols[k].data_ptr() for k in qs._GROUP_FIELDS})
+        ibc = qs.SnapshotInboxC(R=ib.R, C=ib.C, **{k: v.data_ptr() for k, v in ib.t.items()})
+        so = qs.SnapshotOutC(sflags=res.sflags.data_ptr(), resp_type=res.resp_type.data_ptr(),
+                             resp_term=res.resp_term.data_ptr(), resp_index=res.resp_index.data_ptr())
+        keep = (sg, ibc, so)
+        return lambda: _lib.check(fn(C.byref(keep[0]), C.byref(keep[1]), C.byref(keep[2]),
+                                     res.stats.data_ptr(), sp), "qb_dev_follower_snapshot")
+
+    def put_back():
+        for k, v in pristine.items():
+            cols[k].copy_(v)
+
+    def timed(groups):
+        ib = inbox_of(groups)
+        res = qs.new_snapshot_result(ib.R, dev)
+        call = caller(ib, res)
+
+        def sample(ev):
+            put_back()
+            torch.cuda.synchronize()
+            ev.record(ev.ev[0], sp)
+            call()
+            ev.record(ev.ev[1], sp)
+            torch.cuda.synchronize()
+            return ev.elapsed_ms(0, 1) / 1e3
+        ev = HipEvents(2)
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < 0.3:  # warm-up: clocks settle (time_region)
+            sample(ev)
+        res.stats.zero_()
+        ts = [sample(ev) for _ in range(reps)]
+        ev.close()
+        st = res.stats_dict()
+        assert st["restored"] == reps * ib.R and sum(st.values()) == reps * ib.R, st
+        return float(np.median(ts)), ib, res, call
+
+    # Bytes per restoring record, the columns the launch touches (not a traffic
+    # counter).  The record: group 4, from / term / snap_index / snap_term 32,
+    # cs_off 4, five IDs and their list bytes 45 read; sflags 2, resp_type 1,
+    # resp_term 8, resp_index 8 written = 104.  Its group: term, committed,
+    # self_id, last_index 32, role 1, meta 4, pending 1 read = 38; lead 8,
+    # election_elapsed 4, role 1, committed 8, unstable_offset 8, usnap_index 8,
+    # usnap_term 8, last_index 8, last_term 8, first_index 8, run_start 8,
+    # run_term 8, pending 1 written = 94 (meta already holds one run).
+    rec_b, grp_b = 104, 38 + 94
+    every = torch.arange(G, device=dev)
+    shuffled = torch.randperm(G, device=dev)
+    hundredth = every[every % 100 == 0]
+    rows = {}
+    for name, groups in (("all", shuffled), ("one_percent", hundredth[torch.randperm(
+            int(hundredth.numel()), device=dev)]), ("all_ascending", every)):
+        tm, ib, res, call = timed(groups)
+        b = ib.R * (rec_b + grp_b)
+        rows[name] = {"records": ib.R, "us": tm * 1e6, "bytes": b, "TBs": b / tm / 1e12,
+                      "frac": b / tm / 1e9 / HBM_PEAK_GBS}
+        if name == "all":
+            keep = (ib, res, call)
+    extra = {"unit": "groups/s", "samples": reps, "bytes_per_record": rec_b + grp_b,
+             "timing": "one HIP event pair per call, median over the samples; the state put back "
+                       "outside the timed call; per_launch_us = every group, shuffled",
+             **{f"{k}_{f}": v for k, r in rows.items() for f, v in r.items()}}
+
+    # ---- parity at this size: one call of row (a) from the pristine state ----
+    ib, res, call = keep
+    put_back()
+    res.stats.zero_()
+    torch.cuda.synchronize()
+    sub = np.arange(0, G, 1024)
+    rows_ = (np.arange(MAX_RUNS)[:, None] * G + sub[None, :]).ravel()
+
+    def gather():
+        out = {}
+        for k, dt in P.STATE.items():
+            a = cols[k].cpu().numpy().view(dt)
+            out[k] = (a[rows_] if k in P.ROWS else a[sub]).copy()
+        return out
+    before = gather()
+    call()
+    torch.cuda.synchronize()
+    after = gather()
+    nodes = P.nodes_from_arrays(before)
+    grp = ib.t["group"].cpu().numpy().view(np.uint32)
+    pos = np.flatnonzero(grp % 1024 == 0)
+    where = {int(g): j for j, g in enumerate(sub)}
+    rc = {k: ib.t[k].cpu().numpy().view(dt)[pos] for k, dt in (
+        ("from", np.uint64), ("term", np.uint64), ("snap_index", np.uint64),
+        ("snap_term", np.uint64))}
+    recs = [(where[int(grp[i])], S.Snap(int(rc["from"][k]), int(rc["term"][k]),
+                                        int(rc["snap_index"][k]), int(rc["snap_term"][k]),
+                                        {"voters": list(range(1, n + 1))}))
+            for k, i in enumerate(pos)]
+    ref = S.snapshot_call(nodes, recs)
+    want = P.pack_nodes(nodes, base=before)
+    ok = all(np.array_equal(after[k], want[k]) for k in P.STATE)
+    got = {"sflags": res.sflags, "resp_type": res.resp_type, "resp_term": res.resp_term,
+           "resp_index": res.resp_index}
+    ok = ok and all(np.array_equal(got[k].cpu().numpy().view(dt)[pos], np.array(ref[k], dt))
+                    for k, dt in P.OUT.items())
+    st = res.stats_dict()
+    ok = ok and st == dict(S.new_stats(), restored=G) and ref["stats"]["restored"] == len(sub)
+    extra["parity"] = bool(ok)
+    extra["parity_check"] = (f"tests/snapshot_ref.py over {len(sub)} groups (every 1024th) of the "
+                             f"{G}: sflags, the response and the eighteen state columns behind one "
+                             f"call of row (a); the batch's counters: {st}")
+    reporter("follower snapshot (every group restores; shuffled arrival order)", G,
+             rows["all"]["us"] / 1e6, rows["all"]["bytes"], extra)
+    assert ok, "snapshot parity failed"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -2224,6 +2394,8 @@ def main():
         requests_config(1 << 22, a.reps)
     if "ready" in which:
         ready_config(1 << 22, a.reps)
+    if "snapshot" in which:
+        snapshot_config(1 << 22, a.reps)
     if "wire-tracker" in which:
         wire_tracker_config(1 << 24, a.reps)
     if "wire-tracker-fused" in which:  # development A/B: the one call alone
