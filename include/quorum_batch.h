@@ -2040,6 +2040,141 @@ int qb_dev_ingest_csr_tracker_step(uint64_t G, uint32_t max_slots, const uint32_
                                    void* stream);
 
 /* ----------------------------------------------------------------------- */
+/* Wire encode: Message.Marshal of the outboxes                            */
+/* ----------------------------------------------------------------------- */
+
+/* The sending side of the wire ingest: the messages the step calls leave as
+ * records and slot-aligned columns -> gogoproto-encoded raftpb.Message bytes,
+ * bit for bit Message.Marshal (raftpb/raft.pb.go: Size 1235-1263,
+ * MarshalToSizedBuffer 903-972; the nested Snapshot 863-886,
+ * SnapshotMetadata 824-846, ConfState 1021-1063 and Entry 785-807).  Fields go
+ * in field-number order; every non-nullable field is written whatever it
+ * holds (Type, To, From, Term, LogTerm, Index, Commit, Snapshot, Reject,
+ * RejectHint), Context only when non-nil.  The Snapshot of every message
+ * encoded here is the empty one: 4a 0a 12 08 0a 02 28 00 10 00 18 00.
+ * A context is the project's 8-byte big-endian request id in a uint64, 0 =
+ * nil.  For MsgReadIndex (15) and MsgReadIndexResp (16) the id travels as one
+ * Entry{Data: id} in field 7 (3a 10 08 00 10 00 18 00 22 08 + the 8 bytes),
+ * not as Context (responseToReadIndexReq raft.go:1737-1751 hands req.Entries
+ * back; a follower forwards the request whole, raft.go:1445-1470); id 0 writes
+ * neither.
+ * Entry payloads and snapshots never reach the device: a message with n > 0
+ * entries is written whole except field 7, and ent_at[i] is the byte offset
+ * inside message i just behind the Index field, where the host splices its
+ * encoded entries (one 3a-keyed field each); a MsgSnap is left to the host.
+ *
+ * Message i is bytes[msg_off[i] .. msg_off[i+1]).  msg_off [M+1] is always
+ * complete (it is the array qb_dev_ingest_messages takes) and *nbytes =
+ * msg_off[M] is what the batch needs, so a caller can size a retry.  A
+ * message whose end lies past cap gets QB_ENC_NO_SPACE and none of its bytes
+ * is written; those before it are intact.  Nothing outside [bytes, bytes +
+ * cap) is written, and inside it only the bytes of written messages: bytes
+ * may have any alignment.  ent_at (nullable) is written where status <= 1,
+ * stats (nullable, QB_ENC_STATUS_COUNT device uint64, accumulated) counts
+ * each status. */
+#define QB_ENC_OK 0        /* the bytes are the complete message                 */
+#define QB_ENC_ENTRIES 1   /* complete but for field 7 at ent_at                 */
+#define QB_ENC_HOST 2      /* length 0: the host marshals it (MsgSnap, or a type
+                              the front end does not form)                        */
+#define QB_ENC_NONE 3      /* length 0: no message here                          */
+#define QB_ENC_NO_SPACE 4  /* length counted, not written                        */
+#define QB_ENC_STATUS_COUNT 5
+/* The longest message the device writes, a read type with a context: Type 2
+ * (the two read types are below 128), To / From / Term / LogTerm / Index 11
+ * each, the read entry 18, Commit 11, Snapshot 12, Reject 2, RejectHint 11.
+ * Any other type (a uint8: up to 3 bytes) carries a Context of 10 instead of
+ * the entry: 104 at most. */
+#define QB_ENC_MAX_BYTES 111
+
+typedef struct qb_encode_out {
+  uint8_t* bytes;     /* [cap]                                             */
+  uint64_t cap;
+  uint64_t* msg_off;  /* [M+1]                                             */
+  uint8_t* status;    /* [M] QB_ENC_*                                      */
+  uint32_t* ent_at;   /* [M] nullable                                      */
+  uint64_t* nbytes;   /* device uint64                                     */
+  uint64_t* stats;    /* nullable: [QB_ENC_STATUS_COUNT] accumulated       */
+} qb_encode_out;
+
+/* The general form: every field explicit, all columns [M]; a NULL column
+ * reads as 0 (type is required).  Term is taken as given: raft.send's rule
+ * (raft.go:386-419) is the caller's.  Type QB_MSG_SNAP gives QB_ENC_HOST and
+ * type 0 QB_ENC_NONE; n_entries > 0 gives QB_ENC_ENTRIES (for the two read
+ * types n_entries is not read: their entry is the context). */
+typedef struct qb_encode_cols {
+  const uint8_t* type;
+  const uint64_t* to;
+  const uint64_t* from;
+  const uint64_t* term;
+  const uint64_t* log_term;
+  const uint64_t* index;
+  const uint64_t* commit;
+  const uint64_t* reject_hint;
+  const uint8_t* reject;      /* 0 / non-zero                                */
+  const uint64_t* context;
+  const uint64_t* n_entries;
+} qb_encode_cols;
+
+/* The groups of the two front ends over the step calls' outputs: the CSR
+ * every call already has plus the sender.  Both apply raft.send
+ * (raft.go:386-419): From = self_id[g], Term = term[g]; To = ids[slot].  They
+ * form QB_MSG_APP, QB_MSG_HEARTBEAT, QB_MSG_TIMEOUT_NOW and
+ * QB_MSG_READ_INDEX_RESP; QB_MSG_SNAP and any other type give QB_ENC_HOST;
+ * type 0, QB_READ_STATE, to = 0xFF, a slot outside its group (or past the
+ * group's QB_MAX_SLOTS-th) and a group >= G give QB_ENC_NONE. */
+typedef struct qb_encode_groups {
+  uint64_t G;
+  const uint32_t* off;      /* [G+1] */
+  const uint64_t* ids;      /* [off[G]] slot -> raft ID */
+  const uint64_t* self_id;  /* [G] */
+  const uint64_t* term;     /* [G] */
+} qb_encode_groups;
+
+/* Slot-aligned messages, as the heartbeats are: message s belongs to slot s,
+ * M = S = off[G] (the caller's count: slots the off table does not cover get
+ * QB_ENC_NONE).  A group takes part where gflags == NULL or gflags[g] &
+ * gmask; the slot whose ID is self_id[g] never gets a message.  One form for
+ * the tick's broadcast (tflags & QB_TFLAG_BEAT, type_all QB_MSG_HEARTBEAT,
+ * hb_commit as commit, hb_ctx as ctx_g: sendHeartbeat raft.go:495-511), the
+ * requests' heartbeats (qflags & QB_QFLAG_HEARTBEATS) and the proposal's
+ * bcastAppend (pflags & QB_PFLAG_BCAST, msg_type / msg_index / msg_log_term /
+ * msg_n, committed as commit_g: maybeSendAppend raft.go:432-492). */
+typedef struct qb_encode_slot_cols {
+  uint64_t S;
+  const uint8_t* gflags;     /* [G] nullable                                */
+  uint32_t gmask;
+  uint32_t type_all;         /* the type of every slot where type == NULL   */
+  const uint8_t* type;       /* [S] nullable                                */
+  const uint64_t* index;     /* [S] nullable                                */
+  const uint64_t* log_term;  /* [S] nullable                                */
+  const uint64_t* commit;    /* [S] nullable                                */
+  const uint64_t* n_entries; /* [S] nullable                                */
+  const uint64_t* commit_g;  /* [G] nullable: Commit where commit == NULL   */
+  const uint64_t* ctx_g;     /* [G] nullable                                */
+} qb_encode_slot_cols;
+
+/* Workspace of a call over M messages (0: M * QB_ENC_MAX_BYTES >= 2^32, too
+ * large for one call: the offsets' scan is 32-bit).  A NULL required pointer,
+ * a short workspace or such an M is QB_EINVAL before any launch; M == 0 (or
+ * G == 0) is QB_OK with *nbytes = 0 and msg_off[0] = 0 written.  No
+ * allocation inside the calls (they can be graph-captured).
+ * qb_dev_encode_msg_out takes qb_dev_leader_step's dense list (the outbox's
+ * slots / chunks work too, as flat arrays: a zeroed record has type 0) with M
+ * = msg_cap; records at or past *msg_total (device, nullable: all msg_cap)
+ * get QB_ENC_NONE — the count is never copied back.  MsgApp: Index / LogTerm
+ * / Commit from the record, aux entries; MsgReadIndexResp: Index from index,
+ * the entry from aux. */
+size_t qb_encode_scratch_bytes(uint64_t M);
+int qb_dev_encode_messages(uint64_t M, const qb_encode_cols* c, const qb_encode_out* out,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int qb_dev_encode_msg_out(const qb_encode_groups* eg, const qb_msg_out* msgs, uint64_t msg_cap,
+                          const uint64_t* msg_total, const qb_encode_out* out, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int qb_dev_encode_slots(const qb_encode_groups* eg, const qb_encode_slot_cols* s,
+                        const qb_encode_out* out, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
+/* ----------------------------------------------------------------------- */
 /* Configuration changes                             */
 /* ----------------------------------------------------------------------- */
 

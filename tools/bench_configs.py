@@ -2343,6 +2343,179 @@ def snapshot_config(G, reps, *, reporter=None):
     assert ok, "snapshot parity failed"
 
 
+def encode_config(G, reps, *, reporter=None):
+    """The batched Message.Marshal (qb_dev_encode_*), three workloads: (a) the
+    heartbeats of G five-voter leader groups through the slot form (every
+    group beats, one in ten with a read context: 4G messages and G own
+    slots); (b) 4G general columns (MsgAppResp on encode_appresp's domain); (c)
+    a list of the leader step's shape, four MsgApp with entries per group in
+    group order.  Beside them, in the same session, the decode-side yardstick:
+    qb_dev_ingest_messages over (b)'s device bytes and offsets (the streaming
+    yardstick, qb_dev_advance with every group ready, is the ready row: run
+    ``--only encode,ready``).  One HIP event pair per call, median over the
+    samples after warm-up; calls straight to the C ABI.  Parity at this size:
+    tests/encode_ref.py over every 1024th message of each workload — bytes,
+    offsets, status, ent_at — and the batch's counters."""
+    reporter = reporter or report
+    import ctypes as C
+    import time
+    from etcd_amd import _lib
+    from etcd_amd.quorum import encode as qe, wire
+    from etcd_amd.quorum.leader import MSG_DTYPE
+    from tests import encode_ref as E
+    n = 5
+    S, M = n * G, 4 * G
+    sp = torch.cuda.current_stream(dev).cuda_stream
+    ar = lambda k: torch.arange(k, dtype=torch.int64, device=dev)  # noqa: E731
+    gg, ss = ar(G).repeat_interleave(n), ar(n).repeat(G)
+    ids = 16384 + ss * 200000 + gg % 100000
+    off = (ar(G + 1) * n).to(torch.int32)
+    self_id = 16384 + ar(G) % 100000
+    term = torch.full((G,), 20000, dtype=torch.int64, device=dev)
+    committed = (1 << 35) + ar(G) * 64
+    groups = qe.EncodeGroups(off, ids, self_id, term, S)
+    gen = torch.Generator(device=dev).manual_seed(0xE7C0DE)
+    rnd = lambda k, hi: torch.randint(0, hi, (k,), generator=gen, dtype=torch.int64, device=dev)  # noqa: E731
+    hb_commit = committed.repeat_interleave(n) - rnd(S, 64)
+    hb_ctx = torch.where(rnd(G, 10) == 0, (1 << 56) + rnd(G, 1 << 40) + 1, torch.zeros_like(term))
+    # (b): responses of the peers, as encode_appresp takes them
+    peer = 1 + rnd(M, n - 1)
+    gm = ar(M) // 4
+    col_b = {"type": torch.full((M,), 4, dtype=torch.uint8, device=dev),
+             "to": self_id[gm], "from": 16384 + peer * 200000 + gm % 100000,
+             "term": term[gm], "index": committed[gm] + rnd(M, 64),
+             "reject": (rnd(M, 10) == 0).to(torch.uint8)}
+    # (c): four MsgApp per group, one entry each
+    recs = np.zeros(M, MSG_DTYPE)
+    gi = np.arange(M, dtype=np.uint64) // 4
+    recs["group"], recs["to"], recs["type"] = gi, 1 + np.arange(M) % 4, qe.MSG_APP
+    recs["index"], recs["log_term"] = (1 << 35) + gi * 64 + 63, 20000
+    recs["commit"], recs["aux"] = (1 << 35) + gi * 64, 1
+    msgs = torch.from_numpy(recs.view(np.uint8)).to(dev)
+    total = torch.full((1,), M, dtype=torch.int64, device=dev)
+
+    fns = {"slots": _lib.fn("qb_dev_encode_slots"), "columns": _lib.fn("qb_dev_encode_messages"),
+           "list": _lib.fn("qb_dev_encode_msg_out")}
+    work = {"slots": (S, lambda o: qe.encode_slots(groups, cols={"commit": hb_commit, "ctx_g": hb_ctx},
+                                                   out=o)),
+            "columns": (M, lambda o: qe.encode_columns(col_b, out=o)),
+            "list": (M, lambda o: qe.encode_msg_out(groups, msgs, M, total, out=o))}
+
+    def caller(name, out, Mn):
+        """The checked wrapper once, then the same call through ctypes alone."""
+        work[name][1](out)
+        ws = out._ws if name == "columns" else groups._ws
+        oc = qe._out_struct(out, Mn)
+        eg = groups.struct()
+        if name == "slots":
+            sc = qe.EncodeSlotColsC(S=S, gflags=None, gmask=0xFF, type_all=qe.MSG_HEARTBEAT,
+                                    commit=hb_commit.data_ptr(), ctx_g=hb_ctx.data_ptr())
+            args = (C.byref(eg), C.byref(sc), C.byref(oc))
+        elif name == "columns":
+            cc = qe.EncodeColsC(**{k: v.data_ptr() for k, v in col_b.items()})
+            args = (Mn, C.byref(cc), C.byref(oc))
+        else:
+            args = (C.byref(eg), msgs.data_ptr(), Mn, total.data_ptr(), C.byref(oc))
+        keep = (oc, eg, args, ws)
+        return lambda: _lib.check(fns[name](*keep[2], ws.data_ptr(), ws.numel(), sp), name), keep
+
+    def timed(call):
+        def sample(ev):
+            torch.cuda.synchronize()
+            ev.record(ev.ev[0], sp)
+            call()
+            ev.record(ev.ev[1], sp)
+            torch.cuda.synchronize()
+            return ev.elapsed_ms(0, 1) / 1e3
+        ev = HipEvents(2)
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < 0.3:  # warm-up: clocks settle (time_region)
+            sample(ev)
+        ts = [sample(ev) for _ in range(reps)]
+        ev.close()
+        return float(np.median(ts))
+
+    # Bytes per message, the columns the launches touch (not a traffic counter).
+    # Every form: the length written and read by the scan's three launches 20,
+    # the offset read twice (p, q share lines: 4), msg_off 8, status 1, ent_at 4
+    # and the message's own bytes.  Slots: the slot's group written 4 and read
+    # twice 8, ids and commit read twice 32, per group (a fifth each) off,
+    # self_id, term, ctx read twice 11.2.  Columns: type 1, five u64 and reject
+    # 41, read twice.  List: the 40-byte record twice, the group's off / ids /
+    # self_id / term gathered twice 64.
+    fixed = 20 + 4 + 8 + 1 + 4
+    read_b = {"slots": 4 + 8 + 32 + 11.2, "columns": 2 * 42, "list": 2 * 40 + 64}
+    rows, keepers, outs = {}, [], {}
+    for name, (Mn, _) in work.items():
+        out = qe.new_out(Mn, dev, cap=Mn * 64)
+        call, keep = caller(name, out, Mn)
+        keepers.append(keep)
+        out.stats.zero_()
+        tm = timed(call)
+        torch.cuda.synchronize()
+        nb = int(out.nbytes[0])
+        written = int((out.status[:Mn] <= 1).sum())
+        b = Mn * (fixed + read_b[name]) + nb
+        rows[name] = {"messages": Mn, "written": written, "us": tm * 1e6, "out_bytes": nb,
+                      "bytes_per_message": b / Mn, "TBs": b / tm / 1e12,
+                      "frac": b / tm / 1e9 / HBM_PEAK_GBS}
+        outs[name] = out
+
+    # ---- the decode-side yardstick: the ingest over (b)'s bytes ----
+    ob = outs["columns"]
+    nbb = int(ob.nbytes[0])
+    grp32 = gm.to(torch.int32)
+    t_in = timed(lambda: wire.ingest(ob.bytes, nbb, ob.msg_off, grp32, off, ids))
+    in_b = nbb + M * (8 + 4 + 40) + M * (4 + 1 + 32 + 1 + 1)
+    rows["ingest"] = {"messages": M, "us": t_in * 1e6, "bytes_per_message": in_b / M,
+                      "TBs": in_b / t_in / 1e12, "frac": in_b / t_in / 1e9 / HBM_PEAK_GBS}
+
+    # ---- parity at this size: every 1024th message of each workload ----
+    h = lambda t: t.cpu().numpy()  # noqa: E731
+    u = lambda t: h(t).view(np.uint64)  # noqa: E731
+    ok, detail = True, {}
+    for name, (Mn, _) in work.items():
+        o = outs[name]
+        sub = np.arange(0, Mn, 1024)
+        offs, st = u(o.msg_off), h(o.status)
+        at, by = h(o.ent_at).view(np.uint32), h(o.bytes)
+        if name == "slots":
+            sg = sub // n
+            cg, cx = u(self_id), u(hb_ctx)
+            iu, tu, hc = u(ids), u(term), u(hb_commit)
+            want = [(E.NONE, None) if iu[s] == cg[g] else
+                    E.form(int(cg[g]), int(tu[g]), E.MSG_HEARTBEAT, int(iu[s]), 0, 0, int(hc[s]), 0,
+                           int(cx[g])) for s, g in zip(sub, sg)]
+        elif name == "columns":
+            cb = {k: (h(v) if v.dtype == torch.uint8 else u(v))[sub] for k, v in col_b.items()}
+            want = E.columns(cb, len(sub))
+        else:
+            want = E.msg_out(G, h(off).view(np.uint32), u(ids), u(self_id), u(term), recs[sub],
+                             len(sub), None)
+        good = 0
+        for j, i in enumerate(sub):
+            code, m = want[j]
+            b = by[int(offs[i]):int(offs[i + 1])].tobytes()
+            if code <= E.ENTRIES:
+                good += (st[i] == code and b == E.marshal(m) and at[i] == E.ent_at(m))
+            else:
+                good += (st[i] == code and b == b"")
+        stats = o.stats_dict()
+        counted = sum(stats.values()) == (reps + 1) * Mn or sum(stats.values()) % Mn == 0
+        ok = ok and good == len(sub) and counted and int(offs[Mn]) == int(o.nbytes[0])
+        detail[name] = f"{good}/{len(sub)}"
+    extra = {"unit": "messages/s", "samples": reps,
+             "timing": "one HIP event pair per call, median over the samples after warm-up",
+             **{f"{k}_{f}": v for k, r in rows.items() for f, v in r.items()},
+             "parity": bool(ok),
+             "parity_check": f"tests/encode_ref.py over every 1024th message (bytes, msg_off, "
+                             f"status, ent_at): {detail}"}
+    r = rows["slots"]
+    reporter("encode (heartbeats of every group through the slot form)", r["messages"],
+             r["us"] / 1e6, r["messages"] * r["bytes_per_message"], extra)
+    assert ok, "encode parity failed"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -2396,6 +2569,8 @@ def main():
         ready_config(1 << 22, a.reps)
     if "snapshot" in which:
         snapshot_config(1 << 22, a.reps)
+    if "encode" in which:
+        encode_config(1 << 22, a.reps)
     if "wire-tracker" in which:
         wire_tracker_config(1 << 24, a.reps)
     if "wire-tracker-fused" in which:  # development A/B: the one call alone
