@@ -107,6 +107,8 @@ SIGNATURES = {
     "qb_wire_csr_tracker_workspace_bytes": (C.c_size_t, [_u64, _u32, _u64]),
     "qb_dev_ingest_csr_tracker_step": (_i32, [_u64, _u32, _p, _p, _u64, _p, _u64] + [_p] * 16 +
                                        [C.c_size_t, _p]),
+    "qb_wire_follower_scratch_bytes": (C.c_size_t, [_u64]),
+    "qb_dev_ingest_follower": (_i32, [_u64, _p, _u64, _p, _p, _u64, _p, _p, C.c_size_t, _p]),
     "qb_encode_scratch_bytes": (C.c_size_t, [_u64]),
     "qb_dev_encode_messages": (_i32, [_u64, _p, _p, _p, C.c_size_t, _p]),
     "qb_dev_encode_msg_out": (_i32, [_p, _p, _u64, _p, _p, _p, C.c_size_t, _p]),

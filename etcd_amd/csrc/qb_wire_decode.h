@@ -9,6 +9,8 @@
 // plus the group-row lookup that maps From to the group's slot.
 #pragma once
 
+#include <type_traits>
+
 #include "qb_common.h"
 
 namespace qb {
@@ -53,6 +55,30 @@ struct LdsSrc {
 struct GlobalSrc {
   const u8* g;
   __device__ __forceinline__ u8 at(u64 i) const { return g[i]; }
+};
+
+// Global memory through an 8-byte register window (qb_follower_wire.hip: a
+// MsgApp with payloads passes the LDS stage, and a byte load per key, length
+// and varint byte from lanes 370 bytes apart moved a cache line each).  The
+// window is one unaligned 8-byte load at the byte asked for, or the
+// buffer's last 8 bytes: nothing outside [g, g + n) is read.  Fields are
+// read in ascending order, so a refill serves the next 8 bytes; a skipped
+// Data or a jump back refills.  A buffer under 8 bytes is read a byte at a
+// time.
+struct WinSrc {
+  const u8* g;
+  u64 n;
+  mutable u64 w = 0;
+  mutable u64 wpos = ~0ull - 7;  // no window: i - wpos >= 8 for every i
+  __device__ __forceinline__ WinSrc(const u8* g_, u64 n_) : g(g_), n(n_) {}
+  __device__ __forceinline__ u8 at(u64 i) const {
+    if (n < 8) return g[i];
+    if (i - wpos >= 8) {  // (unsigned: behind the window, or before it)
+      wpos = i + 8 <= n ? i : n - 8;
+      __builtin_memcpy(&w, g + wpos, 8);
+    }
+    return u8(w >> ((i - wpos) * 8));
+  }
 };
 
 // The generated decoders' varint loop: error at shift >= 64 or at l.
@@ -102,7 +128,7 @@ __device__ __forceinline__ bool varint(const Src& s, u64& i, u64 l, u64& v) {
 
 // skipRaft on [i, l): advances i past one field (with nested groups).
 template <class Src>
-__device__ bool skip_field(const Src& s, u64& i, u64 l) {
+__device__ __forceinline__ bool skip_field_body(const Src& s, u64& i, u64 l) {
   const u64 start = i;
   int depth = 0;
   while (i < l) {
@@ -137,19 +163,43 @@ __device__ bool skip_field(const Src& s, u64& i, u64 l) {
   }
   return false;
 }
+// Out of line for the LDS and plain global sources (as it always was); inline
+// for the windowed source, whose window a call would force into memory.
+template <class Src>
+__device__ bool skip_field(const Src& s, u64& i, u64 l) {
+  return skip_field_body(s, i, l);
+}
+template <>
+__device__ __forceinline__ bool skip_field<WinSrc>(const WinSrc& s, u64& i, u64 l) {
+  return skip_field_body(s, i, l);
+}
 
 struct Fields {
-  u64 type, from, term, log_term, index, reject, hint;
+  u64 type, from, term, log_term, index, commit, reject, hint;
   u64 ctx_pos, ctx_len;
   bool has_ctx;
 };
+
+// The Message decoder's entry sink.  NoSink (the leader's ingest and the
+// composed steps) sees nothing and costs nothing.  Any other Sink has e_term
+// and e_index, which the Entry decoder fills from Term (2) and Index (3) — 0
+// where the field is absent, the last value where it repeats, as Unmarshal —
+// and entry(pre, post), called behind every Entry that unmarshals with the
+// byte range [pre, post) of its field 7, key and length included
+// (qb_follower_wire.hip).
+struct NoSink {};
+// (a namespace-scope flag: a constexpr local in unmarshal changed the register
+// allocation of the leader ingest's deferred launch, though it emits no code)
+template <class Sink>
+constexpr bool kHasSink = !std::is_same<Sink, NoSink>::value;
 
 // The generated Unmarshal of one message kind on [i, l): nested bodies are
 // decoded by the nested kind's own instantiation (the nesting is fixed:
 // Message > Entry | Snapshot > SnapshotMetadata > ConfState), so everything
 // inlines into straight-line code with no private-memory frame stack.
-template <u32 KIND, class Src>
-__device__ __forceinline__ bool unmarshal(const Src& s, u64 i, const u64 l, Fields* f) {
+template <u32 KIND, class Src, class Sink = NoSink>
+__device__ __forceinline__ bool unmarshal(const Src& s, u64 i, const u64 l, Fields* f,
+                                          Sink* sink = nullptr) {
   while (i < l) {
     const u64 pre = i;
     u64 wire;
@@ -180,6 +230,13 @@ __device__ __forceinline__ bool unmarshal(const Src& s, u64 i, const u64 l, Fiel
           case 11: f->hint = v; break;
           default: break;
         }
+        if constexpr (kHasSink<Sink>) {
+          if (fnum == 8) f->commit = v;
+        }
+      }
+      if constexpr (KIND == K_ENTRY && kHasSink<Sink>) {
+        if (fnum == 2) sink->e_term = v;
+        if (fnum == 3) sink->e_index = v;
       }
       continue;
     }
@@ -205,7 +262,16 @@ __device__ __forceinline__ bool unmarshal(const Src& s, u64 i, const u64 l, Fiel
       }
     } else {  // nested message on [i, post)
       bool ok = true;
-      if constexpr (KIND == K_MESSAGE) {
+      if constexpr (KIND == K_MESSAGE && kHasSink<Sink>) {
+        if (nested == K_ENTRY) {
+          sink->e_term = 0;
+          sink->e_index = 0;
+          ok = unmarshal<K_ENTRY>(s, i, post, nullptr, sink);
+          if (ok) sink->entry(pre, post);
+        } else {
+          ok = unmarshal<K_SNAPSHOT>(s, i, post, nullptr);
+        }
+      } else if constexpr (KIND == K_MESSAGE) {
         ok = nested == K_ENTRY ? unmarshal<K_ENTRY>(s, i, post, nullptr)
                                : unmarshal<K_SNAPSHOT>(s, i, post, nullptr);
       } else if constexpr (KIND == K_SNAPSHOT) {
@@ -232,7 +298,8 @@ __device__ __forceinline__ bool unmarshal(const Src& s, u64 i, const u64 l, Fiel
 // decoded exactly as the generic loop decodes it.  The snapshot is consumed
 // only in its common empty form (12 00: an empty SnapshotMetadata).
 template <class Src>
-__device__ __forceinline__ bool fast_prefix(const Src& s, u64& i, const u64 l, Fields& f) {
+__device__ __forceinline__ bool fast_prefix(const Src& s, u64& i, const u64 l, Fields& f,
+                                            u64* commit = nullptr) {
 #define QB_FAST_VARINT(KEY, DST)                     \
   {                                                  \
     if (i >= l || s.at(i) != (KEY)) return true;     \
@@ -249,6 +316,7 @@ __device__ __forceinline__ bool fast_prefix(const Src& s, u64& i, const u64 l, F
   QB_FAST_VARINT(0x28, f.log_term)
   QB_FAST_VARINT(0x30, f.index)
   QB_FAST_VARINT(0x40, ignored)
+  if (commit) *commit = ignored;
   if (i + 4 > l || s.at(i) != 0x4A || s.at(i + 1) != 0x02 || s.at(i + 2) != 0x12 ||
       s.at(i + 3) != 0x00)
     return true;
@@ -309,7 +377,7 @@ __device__ __forceinline__ void fast_field(const u8* lds, u32& o, u32 e, bool& g
 
 template <>
 __device__ __forceinline__ bool fast_prefix<LdsSrc>(const LdsSrc& s, u64& i, const u64 l,
-                                                   Fields& f) {
+                                                   Fields& f, u64* commit) {
   u32 o = u32(i - s.base);
   const u32 e = u32(l - s.base);
   bool go = o < e;
@@ -319,7 +387,7 @@ __device__ __forceinline__ bool fast_prefix<LdsSrc>(const LdsSrc& s, u64& i, con
   fast_field(s.lds, o, e, go, 0x20, &f.term);
   fast_field(s.lds, o, e, go, 0x28, &f.log_term);
   fast_field(s.lds, o, e, go, 0x30, &f.index);
-  fast_field(s.lds, o, e, go, 0x40, nullptr);
+  fast_field(s.lds, o, e, go, 0x40, commit);
   {  // the zero Snapshot as gogoproto writes it — Metadata and its ConfState
      // are non-nullable, AutoLeave / Index / Term always present:
      // 4A 0A 12 08 0A 02 28 00 10 00 18 00 — or with an empty Metadata,
@@ -343,6 +411,45 @@ __device__ __forceinline__ bool fast_prefix<LdsSrc>(const LdsSrc& s, u64& i, con
   }
   i = s.base + o;
   return true;  // errors are the generic loop's to find
+}
+
+// The fast prefix's tail behind the empty Snapshot as gogoproto writes it (the
+// 12 bytes 4A 0A 12 08 0A 02 28 00 10 00 18 00; Go's Marshal and
+// qb_dev_encode_* write no other): Snapshot, Reject, RejectHint and an 8-byte
+// Context.  The generic fast_prefix above stops at that Snapshot (it knows the
+// brief 4A 02 12 00 only, and the leader ingest's launches keep it as it is);
+// a decoder that reads canonical messages from global memory calls this
+// behind it.  The LDS prefix consumes both forms itself, so there this finds
+// nothing to do.  As there, a field is consumed only in its expected form and
+// decoded as the generic loop decodes it.
+template <class Src>
+__device__ __forceinline__ u64 load_be64(const Src& s, u64 i);  // below
+template <class Src>
+__device__ __forceinline__ bool fast_tail12(const Src& s, u64& i, const u64 l, Fields& f) {
+  if (i + 12 > l) return true;
+  const u64 lo = __builtin_bswap64(load_be64(s, i));
+  const u32 hi = u32(s.at(i + 8)) | u32(s.at(i + 9)) << 8 | u32(s.at(i + 10)) << 16 |
+                 u32(s.at(i + 11)) << 24;
+  if (lo != 0x0028020A08120A4Aull || hi != 0x00180010u) return true;
+  i += 12;
+#define QB_FAST_VARINT(KEY, DST)                     \
+  {                                                  \
+    if (i >= l || s.at(i) != (KEY)) return true;     \
+    u64 i2 = i + 1, v;                               \
+    if (!varint_fast(s, i2, l, v)) return false;     \
+    DST = v;                                         \
+    i = i2;                                          \
+  }
+  QB_FAST_VARINT(0x50, f.reject)
+  QB_FAST_VARINT(0x58, f.hint)
+#undef QB_FAST_VARINT
+  if (i + 10 <= l && s.at(i) == 0x62 && s.at(i + 1) == 0x08) {
+    f.has_ctx = true;
+    f.ctx_pos = i + 2;
+    f.ctx_len = 8;
+    i += 10;
+  }
+  return true;
 }
 
 // The 8 bytes at i as a big-endian u64 (the read context's request id).

@@ -4,6 +4,9 @@ device into leader-inbox records for ``LeaderGroups.step``.  Validation is
 the generated gogoproto Message.Unmarshal (raftpb/raft.pb.go:1739-2061)."""
 from __future__ import annotations
 
+import ctypes as C
+from typing import NamedTuple, Optional
+
 import numpy as np
 import torch
 
@@ -13,6 +16,8 @@ from ._dev import grow_workspace, stream_handle
 from .leader import LeaderInbox
 
 WIRE_OK, WIRE_UNMARSHAL, WIRE_TYPE, WIRE_CTX = 0, 1, 2, 3
+WIRE_ENTRIES, WIRE_NO_SPACE = 4, 5  # ingest_follower only
+WIRE_FOLLOWER_STAT_NAMES = ("ok", "unmarshal", "type", "ctx", "entries", "no_space")
 REC_NO_PROGRESS = 0x40
 
 
@@ -144,6 +149,111 @@ def ingest_tracker_step(tracker, buf: torch.Tensor, nbytes: int, msg_off: torch.
         _lib.call("qb_dev_ingest_fixed_tracker_step", tracker.n, tracker.G, M, buf.data_ptr(),
                   nbytes, msg_off.data_ptr(), msg_group.data_ptr(), p(rows), p(off), p(ids), *state)
     return status[:M]
+
+
+class FollowerWireOutC(C.Structure):
+    """struct qb_follower_wire_out (include/quorum_batch.h)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("group", "flags", "from", "term", "index", "aux", "commit",
+                                           "status", "msg_type", "ent_pos", "ent_bytes", "ent_n",
+                                           "ent_off", "ent_term", "ent_len")] +
+                [("ent_cap", C.c_uint64), ("ent_total", C.c_void_p), ("stats", C.c_void_p)])
+
+
+class FollowerIngest(NamedTuple):
+    """What ``ingest_follower`` returns: the two inboxes the follower steps
+    take as they are, and the per-message columns beside them."""
+    inbox: "FollowerInbox"
+    app: "FollowerAppInbox"
+    status: torch.Tensor     # uint8 [M] WIRE_*
+    msg_type: torch.Tensor   # uint8 [M] the low byte of Message.Type
+    ent_pos: torch.Tensor    # int64 [M] the entries' byte range inside buf
+    ent_bytes: torch.Tensor  # int32 [M]
+    ent_n: torch.Tensor      # int32 [M] the entry count
+    ent_total: torch.Tensor  # int64 [1] the runs the batch needs, whatever ent_cap
+
+
+_follower_ws = {}
+
+
+def new_follower_out(M: int, ent_cap: int, device) -> FollowerIngest:
+    """Fresh output tensors of ``ingest_follower`` for M messages and
+    ``ent_cap`` term runs (never empty, so every pointer is valid)."""
+    from .follower import FollowerAppInbox, FollowerInbox
+    n = max(M, 1)
+    e = lambda k, dt: torch.empty(k, dtype=dt, device=device)  # noqa: E731
+    ib = FollowerInbox(e(n, torch.int32), e(n, torch.uint8), e(n, torch.int64), e(n, torch.int64),
+                       e(n, torch.int64), e(n, torch.int64))
+    ib._m = M
+    app = FollowerAppInbox(e(n, torch.int64), e(M + 1, torch.int32), e(max(ent_cap, 1), torch.int64),
+                           e(max(ent_cap, 1), torch.int32), ent_cap)
+    return FollowerIngest(ib, app, e(n, torch.uint8), e(n, torch.uint8), e(n, torch.int64),
+                          e(n, torch.int32), e(n, torch.int32), e(1, torch.int64))
+
+
+def ingest_follower(buf: torch.Tensor, nbytes: int, msg_off: torch.Tensor, msg_group: torch.Tensor,
+                    G: int, *, ent_cap: Optional[int] = None, stats: torch.Tensor = None,
+                    out: Optional[FollowerIngest] = None, stream=None) -> FollowerIngest:
+    """Decode M = len(msg_group) messages to non-leaders into the follower
+    steps' inbox (qb_dev_ingest_follower): MsgHeartbeat, MsgVote / MsgPreVote,
+    MsgTimeoutNow and MsgApp become records, every other type a FIN_HOST
+    record.  ``ent_cap`` is the room for the MsgApp entries' term runs
+    (default ``nbytes // 2``, which no batch exceeds: an entry takes two bytes;
+    a large batch should pass a tighter one and retry with ``ent_total`` where
+    a status is WIRE_NO_SPACE).  ``stats`` (int64 [6], nullable) accumulates
+    the WIRE_* counts.  ``G`` is the step's group count; a group >= G is
+    passed through and stays the step's bad group.  ``out`` (a
+    ``FollowerIngest`` of the caller's tensors, ``out.app.E`` its ent_cap) is
+    written in place of fresh tensors and returned as it is."""
+    from .follower import MAX_RECORDS
+    _check_batch(buf, nbytes, msg_off, msg_group)
+    _check_tensors(((buf, "buf", (torch.uint8,), 0), (stats, "stats", (torch.int64,),
+                                                     len(WIRE_FOLLOWER_STAT_NAMES))))
+    if not isinstance(G, int) or G < 0:
+        raise _lib.QuorumBatchError(f"G must be a non-negative int, got {G!r}")
+    M = msg_group.numel()
+    if M > MAX_RECORDS or nbytes >= 1 << 32:
+        raise _lib.QuorumBatchError(f"batch of {M} messages / {nbytes} bytes too large for one call "
+                                    "(M <= 2^32 - 2, nbytes < 2^32)")
+    dev = buf.device
+    if out is None:
+        cap = nbytes // 2 if ent_cap is None else ent_cap
+        if not isinstance(cap, int) or cap < 0:
+            raise _lib.QuorumBatchError(f"ent_cap must be a non-negative int, got {ent_cap!r}")
+        o = new_follower_out(M, cap, dev)
+    else:
+        if ent_cap is not None and ent_cap != out.app.E:
+            raise _lib.QuorumBatchError(f"ent_cap {ent_cap} is not out.app.E = {out.app.E}")
+        o = out
+        if o.inbox.M != M:
+            raise _lib.QuorumBatchError(f"out.inbox holds {o.inbox.M} records, the batch {M}")
+    ib, app, cap = o.inbox, o.app, o.app.E
+    ib.check()
+    app.check(M)
+    _check_tensors(((buf, "buf", (torch.uint8,), 0), (ib.group, "out.inbox", (torch.int32,), M),
+                    (app.commit, "out.app", (torch.int64,), M),
+                    (o.status, "status", (torch.uint8,), M), (o.msg_type, "msg_type", (torch.uint8,), M),
+                    (o.ent_pos, "ent_pos", (torch.int64,), M),
+                    (o.ent_bytes, "ent_bytes", (torch.int32,), M),
+                    (o.ent_n, "ent_n", (torch.int32,), M),
+                    (o.ent_total, "ent_total", (torch.int64,), 1)))
+    for k in ("status", "msg_type", "ent_pos", "ent_bytes", "ent_n", "ent_total"):
+        if getattr(o, k) is None:
+            raise _lib.QuorumBatchError(f"ingest_follower out: {k} is missing")
+    need = int(_lib.fn("qb_wire_follower_scratch_bytes")(M))
+    key = (dev, stream_handle(dev, stream))  # one workspace per stream: calls on two may overlap
+    ws = _follower_ws[key] = grow_workspace(_follower_ws.get(key), need, dev)
+    c = FollowerWireOutC(ib.group.data_ptr(), ib.flags.data_ptr(), ib.frm.data_ptr(),
+                         ib.term.data_ptr(), ib.index.data_ptr(), ib.aux.data_ptr(),
+                         app.commit.data_ptr(), o.status.data_ptr(), o.msg_type.data_ptr(),
+                         o.ent_pos.data_ptr(), o.ent_bytes.data_ptr(), o.ent_n.data_ptr(),
+                         app.ent_off.data_ptr(), app.ent_term.data_ptr(), app.ent_len.data_ptr(), cap,
+                         o.ent_total.data_ptr(), None if stats is None else stats.data_ptr())
+    _lib.call("qb_dev_ingest_follower", M, buf.data_ptr(), nbytes, msg_off.data_ptr(),
+              msg_group.data_ptr(), G, C.byref(c), ws.data_ptr(), ws.numel(), key[1])
+    if out is not None:
+        return out
+    return o._replace(status=o.status[:M], msg_type=o.msg_type[:M], ent_pos=o.ent_pos[:M],
+                      ent_bytes=o.ent_bytes[:M], ent_n=o.ent_n[:M])
 
 
 # ------------------------------------------------------- workload synth ---

@@ -2039,6 +2039,105 @@ int qb_dev_ingest_csr_tracker_step(uint64_t G, uint32_t max_slots, const uint32_
                                    uint64_t* stats, void* workspace, size_t workspace_bytes,
                                    void* stream);
 
+/* The follower's ingest: raw raftpb.Message bytes -> the inbox of
+ * qb_dev_follower_step / qb_dev_follower_log_step, with no host pass between
+ * them.  bytes, nbytes, msg_off [M+1], msg_group [M] and the validation
+ * (Message.Unmarshal, raftpb/raft.pb.go:1739-2061, with Entry.Unmarshal
+ * 1360-1500 and the nested Snapshot bodies; unknown fields as skipRaft
+ * 2909-2988) are qb_dev_ingest_messages'.  raft.Step checks no membership
+ * for the types a non-leader receives (raft.go:847-984, 939-956), so no
+ * config is read: group[i] = msg_group[i] as given, and a group >= G stays
+ * the step's QB_FSTAT_BAD_GROUP (G is not used otherwise).  Classification
+ * goes by Message.Type as Go holds it, an int32 (the varint's low 32 bits):
+ *
+ *   does not unmarshal, or the slice is not inside the buffer:
+ *     QB_WIRE_UNMARSHAL; group = UINT32_MAX, every other column 0 (the
+ *     transport drops it before Step: rafthttp/stream.go:466).
+ *   MsgHeartbeat (8), Context nil / empty or 8 bytes not all zero:
+ *     QB_FIN_HEARTBEAT, index = Commit, aux = the big-endian id (0: none).
+ *     Any other Context: QB_FIN_HOST, QB_WIRE_CTX.
+ *   MsgVote (5) / MsgPreVote (17): QB_FIN_VOTE / QB_FIN_PREVOTE, index =
+ *     Index, aux = LogTerm; QB_FREC_FORCE iff Context is exactly the 16 bytes
+ *     "CampaignTransfer" (raft.go:854; any other context is not force).
+ *   MsgTimeoutNow (14): QB_FIN_TIMEOUT_NOW; Context ignored (raft.go:1452).
+ *   MsgApp (3): index = Index, aux = LogTerm, commit = Commit, ent_n = the
+ *     number of field-7 fields, whatever the status.  Where those fields are
+ *     one contiguous byte range (or there are none) and their Entry.Index
+ *     are Index + 1, Index + 2, ... (uint64 wrap): QB_FIN_APP, with ent_pos /
+ *     ent_bytes = that range inside bytes (0 / 0 without entries) and the
+ *     entries run-length encoded by Entry.Term in ent_term / ent_len[ent_off[i]
+ *     .. ent_off[i+1]), adjacent runs differing (a Term of 0 is passed on: the
+ *     log step has a rule for it; more than QB_LEADER_MAX_RUNS runs are legal
+ *     here).  Otherwise — a gap, a repeated or out-of-order Index, another
+ *     field between two entries — QB_FIN_HOST, QB_WIRE_ENTRIES, no runs,
+ *     ent_pos = ent_bytes = 0.  A message whose runs end past ent_cap:
+ *     QB_FIN_HOST, QB_WIRE_NO_SPACE, none of its runs written (ent_pos /
+ *     ent_bytes stay); ent_off is monotone, so the messages that fit are a
+ *     prefix, as with the encoder's cap.
+ *   every other type (MsgSnap, MsgProp, the response, read, transfer and
+ *     local types, values above 18): QB_FIN_HOST, QB_WIRE_TYPE.
+ * Every QB_FIN_HOST record keeps group, from and term (index, aux and commit
+ * are 0 unless it is a MsgApp), so the follower step stops the group there in
+ * batch order.  term is Message.Term as sent (0: a local message, as Step
+ * reads it).  Snapshot, Reject, RejectHint and To on these types are
+ * validated and otherwise ignored, as Step ignores them.  commit is 0 for
+ * every type but MsgApp; ent_pos / ent_bytes / ent_n are 0 for every other
+ * type too.
+ *
+ * ent_off [M+1] is complete for every message (empty ranges for all but
+ * QB_FIN_APP records, and for those downgraded to QB_WIRE_NO_SPACE the range
+ * they would have had) and *ent_total = ent_off[M] is what the batch needs,
+ * whatever ent_cap is, so a caller can size a retry.  With these columns
+ * qb_follower_inbox = {M, group, flags, from, term, index, aux} and
+ * qb_follower_app_inbox = {commit, ent_off, ent_term, ent_len, E = ent_cap}.
+ * The host persists the entries it takes from bytes[ent_pos[i] .. ent_pos[i]
+ * + ent_bytes[i]) (one 3a-keyed field each: the mirror of the encoder's
+ * ent_at).  stats (nullable, QB_WIRE_FOLLOWER_STATUS_COUNT device uint64,
+ * accumulated) counts each final status.
+ *
+ * qb_wire_follower_scratch_bytes(M) (the workspace's size, named as the
+ * encoder's is) is 0 for M > 2^32 - 2 (the follower steps' bound, and M + 1
+ * offsets of the 32-bit scan).  A NULL out, ent_off,
+ * ent_total; with M > 0 a NULL msg_off, msg_group, required column (group,
+ * flags, from, term, index, aux, commit, status), bytes with nbytes > 0,
+ * ent_term / ent_len with ent_cap > 0; a short workspace, such an M, or
+ * nbytes >= 2^32 (an entry takes two bytes at least, so below that the run
+ * total fits the 32-bit scan and ent_bytes its column; split the batch) is
+ * QB_EINVAL before any launch.  M == 0 is QB_OK with ent_off[0] = 0 and
+ * *ent_total = 0 written.  No allocation inside the call (it can be
+ * graph-captured); nothing outside [bytes, bytes + nbytes) is read and
+ * nothing outside the caller's arrays written. */
+#define QB_WIRE_ENTRIES 4  /* MsgApp whose entries the device does not take  */
+#define QB_WIRE_NO_SPACE 5 /* MsgApp whose runs end past ent_cap             */
+#define QB_WIRE_FOLLOWER_STATUS_COUNT 6
+
+typedef struct qb_follower_wire_out {
+  uint32_t* group;      /* [M] qb_follower_inbox's six columns                */
+  uint8_t* flags;       /* [M] QB_FIN_* | QB_FREC_FORCE                       */
+  uint64_t* from;       /* [M] */
+  uint64_t* term;       /* [M] */
+  uint64_t* index;      /* [M] */
+  uint64_t* aux;        /* [M] */
+  uint64_t* commit;     /* [M] qb_follower_app_inbox.commit                   */
+  uint8_t* status;      /* [M] QB_WIRE_*                                      */
+  uint8_t* msg_type;    /* [M] nullable: the low byte of Message.Type         */
+  uint64_t* ent_pos;    /* [M] nullable                                       */
+  uint32_t* ent_bytes;  /* [M] nullable                                       */
+  uint32_t* ent_n;      /* [M] nullable: the entry count                      */
+  uint32_t* ent_off;    /* [M+1]                                              */
+  uint64_t* ent_term;   /* [ent_cap]                                          */
+  uint32_t* ent_len;    /* [ent_cap]                                          */
+  uint64_t ent_cap;
+  uint64_t* ent_total;  /* device uint64                                      */
+  uint64_t* stats;      /* nullable: [QB_WIRE_FOLLOWER_STATUS_COUNT]          */
+} qb_follower_wire_out;
+
+size_t qb_wire_follower_scratch_bytes(uint64_t M);
+int qb_dev_ingest_follower(uint64_t M, const uint8_t* bytes, uint64_t nbytes,
+                           const uint64_t* msg_off, const uint32_t* msg_group, uint64_t G,
+                           const qb_follower_wire_out* out, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* ----------------------------------------------------------------------- */
 /* Wire encode: Message.Marshal of the outboxes                            */
 /* ----------------------------------------------------------------------- */

@@ -2516,6 +2516,184 @@ def encode_config(G, reps, *, reporter=None):
     assert ok, "encode parity failed"
 
 
+def follower_wire_config(M, reps, *, reporter=None):
+    """The follower's wire ingest (qb_dev_ingest_follower), three workloads:
+    (a) M heartbeats with the bytes qb_dev_encode_slots writes (encoded on the
+    device through the general columns, one in ten with a read context); (b) M
+    MsgApp with no entries; (c) M / 4 MsgApp of 4 entries in 1-2 term runs
+    with 64-byte Data (fixed layout, built on the device).  Beside them, in
+    the same session, qb_dev_ingest_messages_rows over M MsgAppResp.  One HIP
+    event pair per call, median over the samples after warm-up; calls straight
+    to the C ABI.  Parity at this size: tests/follower_wire_ref.py over every
+    1024th message of each workload — every column, the entry range, the runs —
+    and the batch's counters."""
+    reporter = reporter or report
+    import ctypes as C
+    import time
+    from etcd_amd import _lib
+    from etcd_amd.quorum import encode as qe, wire
+    from tests import follower_wire_ref as FW
+    G = 1 << 22
+    sp = torch.cuda.current_stream(dev).cuda_stream
+    ar = lambda k: torch.arange(k, dtype=torch.int64, device=dev)  # noqa: E731
+    gen = torch.Generator(device=dev).manual_seed(0xF0110)
+    rnd = lambda k, hi: torch.randint(0, hi, (k,), generator=gen, dtype=torch.int64, device=dev)  # noqa: E731
+    u8 = lambda k, v: torch.full((k,), v, dtype=torch.uint8, device=dev)  # noqa: E731
+
+    def fields(Mn):
+        gm = rnd(Mn, G)
+        return gm, {"to": 16384 + (1 + rnd(Mn, 4)) * 200000 + gm % 100000, "from": 16384 + gm % 100000,
+                    "term": torch.full((Mn,), 20000, dtype=torch.int64, device=dev),
+                    "commit": (1 << 35) + gm * 64 + rnd(Mn, 64)}
+
+    def columns(cols, Mn):
+        b, moff, st, _, nb = qe.encode_columns(cols, M=Mn)
+        torch.cuda.synchronize()
+        assert int(st.max()) == qe.ENC_OK
+        return b, int(nb[0]), moff
+
+    work = {}
+    gm, f = fields(M)
+    f["type"] = u8(M, 8)
+    f["context"] = torch.where(rnd(M, 10) == 0, (1 << 56) + rnd(M, 1 << 40) + 1, torch.zeros_like(gm))
+    work["heartbeats"] = (M, gm.to(torch.int32), *columns(f, M), 0)
+    gm, f = fields(M)
+    f["type"], f["log_term"], f["index"] = u8(M, 3), f["term"] - 1, f["commit"] + 64
+    work["app_empty"] = (M, gm.to(torch.int32), *columns(f, M), 0)
+    # (c): fixed layout — type 3, to / from / term / logTerm of 3 varint bytes,
+    # index and commit of 6, 4 entries of 79 bytes (Type 0, Term 3, Index 6,
+    # 64-byte Data), the empty Snapshot, Reject 0, RejectHint 0
+    Mc = M // 4
+    gm, f = fields(Mc)
+    index = f["commit"] + 64
+    split = 1 + rnd(Mc, 4)  # entries behind `split` carry term + 1: 4 gives one run
+    lay = [0x08, 3, 0x10, ("v", f["to"], 3), 0x18, ("v", f["from"], 3), 0x20, ("v", f["term"], 3),
+           0x28, ("v", f["term"] - 1, 3), 0x30, ("v", index, 6)]
+    for k in range(4):
+        lay += [0x3A, 79, 0x08, 0, 0x10, ("v", f["term"] - 1 + (split <= k).to(torch.int64), 3),
+                0x18, ("v", index + 1 + k, 6), 0x22, 64] + [0x61 + k] * 64
+    lay += [0x40, ("v", f["commit"], 6), 0x4A, len(wire._EMPTY_SNAPSHOT)] + list(wire._EMPTY_SNAPSHOT)
+    lay += [0x50, 0, 0x58, 0]
+    L = sum(x[2] if isinstance(x, tuple) else 1 for x in lay)
+    buf = torch.empty((Mc, L), dtype=torch.uint8, device=dev)
+    c = 0
+    for x in lay:
+        if isinstance(x, tuple):
+            for col in wire._dev_varint(x[1], x[2]):
+                buf[:, c] = col
+                c += 1
+        else:
+            buf[:, c] = x
+            c += 1
+    work["app_entries"] = (Mc, gm.to(torch.int32), buf.reshape(-1), Mc * L, ar(Mc + 1) * L, 2 * Mc)
+    runs_c = int((split < 4).sum()) + Mc
+
+    def timed(call):
+        def sample(ev):
+            torch.cuda.synchronize()
+            ev.record(ev.ev[0], sp)
+            call()
+            ev.record(ev.ev[1], sp)
+            torch.cuda.synchronize()
+            return ev.elapsed_ms(0, 1) / 1e3
+        ev = HipEvents(2)
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < 0.3:  # warm-up: clocks settle (time_region)
+            sample(ev)
+        ts = [sample(ev) for _ in range(reps)]
+        ev.close()
+        return float(np.median(ts))
+
+    # Bytes per message, the columns the launches touch (not a traffic counter):
+    # msg_off 8 and msg_group 4 read; pass 1 writes group 4, flags 1, from / term
+    # / index / aux / commit 40, status 1, msg_type 1, ent_pos 8, ent_bytes 4,
+    # ent_n 4 and the run count 4 = 67; the scan reads and writes ent_off twice
+    # 16; pass 2 reads status 1 and two offsets 8; plus the message's own bytes
+    # (read once; the entries' keys and varints a second time by pass 2) and 12
+    # per run written.
+    fixed = 12 + 67 + 16 + 9
+    fn = _lib.fn("qb_dev_ingest_follower")
+    need = int(_lib.fn("qb_wire_follower_scratch_bytes")(M))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    stats = torch.zeros(len(wire.WIRE_FOLLOWER_STAT_NAMES), dtype=torch.int64, device=dev)
+    h = lambda t: t.cpu().numpy()  # noqa: E731
+    u = lambda t: h(t).view(np.uint64)  # noqa: E731
+    rows, ok, detail = {}, True, {}
+    for name, (Mn, grp, b, nb, moff, cap) in work.items():
+        o = wire.new_follower_out(Mn, cap, dev)
+        ib, app = o.inbox, o.app
+        oc = wire.FollowerWireOutC(ib.group.data_ptr(), ib.flags.data_ptr(), ib.frm.data_ptr(),
+                                   ib.term.data_ptr(), ib.index.data_ptr(), ib.aux.data_ptr(),
+                                   app.commit.data_ptr(), o.status.data_ptr(), o.msg_type.data_ptr(),
+                                   o.ent_pos.data_ptr(), o.ent_bytes.data_ptr(), o.ent_n.data_ptr(),
+                                   app.ent_off.data_ptr(), app.ent_term.data_ptr(),
+                                   app.ent_len.data_ptr(), cap, o.ent_total.data_ptr(), stats.data_ptr())
+        call = lambda: _lib.check(fn(Mn, b.data_ptr(), nb, moff.data_ptr(), grp.data_ptr(), G,  # noqa: E731,B023
+                                     C.byref(oc), ws.data_ptr(), need, sp), "qb_dev_ingest_follower")  # noqa: B023
+        stats.zero_()
+        tm = timed(call)
+        torch.cuda.synchronize()
+        total = int(o.ent_total[0])
+        by = Mn * fixed + nb + 12 * total
+        rows[name] = {"messages": Mn, "us": tm * 1e6, "in_bytes": nb, "runs": total,
+                      "bytes_per_message": by / Mn, "TBs": by / tm / 1e12,
+                      "frac": by / tm / 1e9 / HBM_PEAK_GBS}
+        # ---- parity: every 1024th message against the restatement ----
+        sub = np.arange(0, Mn, 1024)
+        offs, gh = u(moff), h(grp).view(np.uint32)
+        idx = torch.from_numpy(sub).to(dev)
+        start = moff[idx]
+        lens = moff[idx + 1] - start
+        so = torch.zeros(len(sub) + 1, dtype=torch.int64, device=dev)
+        so[1:] = torch.cumsum(lens, 0)
+        src = torch.repeat_interleave(start - so[:-1], lens) + ar(int(so[-1]))
+        raw, so = h(b[src]).tobytes(), h(so)
+        got = {"group": h(ib.group).view(np.uint32), "flags": h(ib.flags), "frm": u(ib.frm),
+               "term": u(ib.term), "index": u(ib.index), "aux": u(ib.aux), "commit": u(app.commit),
+               "status": h(o.status), "msg_type": h(o.msg_type), "ent_pos": u(o.ent_pos),
+               "ent_bytes": h(o.ent_bytes).view(np.uint32), "ent_n": h(o.ent_n).view(np.uint32)}
+        eo, et, el = h(app.ent_off).view(np.uint32), u(app.ent_term), h(app.ent_len).view(np.uint32)
+        good = 0
+        for j, i in enumerate(sub):
+            w = FW.decode(raw[so[j]:so[j + 1]], int(gh[i]))
+            if w["ent_bytes"]:
+                w["ent_pos"] += int(offs[i])
+            same = all(int(got[k][i]) == w[k] for k, _ in FW.COLUMNS)
+            a, z = int(eo[i]), int(eo[i + 1])
+            good += same and list(zip(et[a:z].tolist(), el[a:z].tolist())) == w["runs"]
+        st = h(stats).view(np.uint64)
+        counted = int(st.sum()) % Mn == 0 and int(st[FW.OK]) == int(st.sum())
+        want_total = {"heartbeats": 0, "app_empty": 0, "app_entries": runs_c}[name]
+        ok = ok and good == len(sub) and counted and total == want_total == int(eo[Mn])
+        detail[name] = f"{good}/{len(sub)}"
+
+    # ---- the leader's ingest over the same count of MsgAppResp, same session ----
+    gm = rnd(M, G)
+    n = 5
+    gg, ss = ar(G).repeat_interleave(n), ar(n).repeat(G)
+    ids = 16384 + ss * 200000 + gg % 100000
+    off = (ar(G + 1) * n).to(torch.int32)
+    bb, nbb, mo = wire.encode_appresp(16384 + gm % 100000, 16384 + (1 + rnd(M, 4)) * 200000 + gm % 100000,
+                                      torch.full((M,), 20000, dtype=torch.int64, device=dev),
+                                      (1 << 35) + gm * 64 + rnd(M, 64), (rnd(M, 10) == 0).to(torch.uint8))
+    grows = wire.group_rows(off, ids)
+    g32 = gm.to(torch.int32)
+    t_in = timed(lambda: wire.ingest(bb, nbb, mo, g32, off, ids, rows=grows))
+    in_b = nbb + M * (8 + 4 + 64) + M * (4 + 1 + 32 + 1 + 1)
+    rows["ingest_rows"] = {"messages": M, "us": t_in * 1e6, "bytes_per_message": in_b / M,
+                           "TBs": in_b / t_in / 1e12, "frac": in_b / t_in / 1e9 / HBM_PEAK_GBS}
+    extra = {"unit": "messages/s", "samples": reps,
+             "timing": "one HIP event pair per call, median over the samples after warm-up",
+             **{f"{k}_{f}": v for k, r in rows.items() for f, v in r.items()},
+             "parity": bool(ok),
+             "parity_check": f"tests/follower_wire_ref.py over every 1024th message (every column, "
+                             f"the entry range, the runs): {detail}"}
+    r = rows["heartbeats"]
+    reporter("follower wire ingest (heartbeats as the slot form writes them)", r["messages"],
+             r["us"] / 1e6, r["messages"] * r["bytes_per_message"], extra)
+    assert ok, "follower wire parity failed"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -2571,6 +2749,8 @@ def main():
         snapshot_config(1 << 22, a.reps)
     if "encode" in which:
         encode_config(1 << 22, a.reps)
+    if "follower-wire" in which:
+        follower_wire_config(1 << 24, a.reps)
     if "wire-tracker" in which:
         wire_tracker_config(1 << 24, a.reps)
     if "wire-tracker-fused" in which:  # development A/B: the one call alone
