@@ -115,6 +115,7 @@ SIGNATURES = {
     "qb_dev_encode_slots": (_i32, [_p, _p, _p, _p, C.c_size_t, _p]),
     "qb_conf_change_workspace_bytes": (C.c_size_t, [_u64]),
     "qb_dev_conf_change": (_i32, [_p, _p, _p, C.c_size_t, _p]),
+    "qb_dev_switch_config": (_i32, [_p, _p, _p, _p, _p]),
     "qb_shard_range": (_i32, [_u64, _i32, _i32, _p, _p]),
     "qb_comm_get_unique_id": (_i32, [_p]),
     "qb_comm_init": (_i32, [C.POINTER(C.c_void_p), _i32, _i32, _p]),

@@ -1,5 +1,6 @@
 // qb_span_tile.h — the shape the streaming step kernels share (k_tick,
-// k_campaign, k_propose, k_requests): one pass with no cross-group dependence.
+// k_campaign, k_propose, k_requests, k_switch): one pass with no cross-group
+// dependence.
 //
 // A workgroup takes tiles of 256 consecutive groups, which own one contiguous
 // slot span [off[g0], off[gend]).  A group phase runs a thread per group and
@@ -139,8 +140,10 @@ __device__ __forceinline__ u64 walk_runs(const void* run_start, const void* run_
 // / ments are the log's bounds and the entries per message; term_prev() gives
 // term(nx - 1) and is called only for a slot that is not paused.  The message
 // goes to *mi (index), *ml (log term), *mn (entries).  Returns its type (0:
-// none).
-template <class Groups, class TermPrev>
+// none).  SendIfEmpty = false is maybeSendAppend(to, false): an empty entry
+// list, a compacted next included, returns before the snapshot fallback
+// (raft.go:442-444).
+template <bool SendIfEmpty = true, class Groups, class TermPrev>
 __device__ __forceinline__ u32 maybe_send_append(const Groups& pg, u64 g, u64 i, u64 nx, u8 st,
                                                  u32 ipos, u64 first, u64 last, u64 ments,
                                                  TermPrev term_prev, u64* mi, u64* ml, u64* mn) {
@@ -160,6 +163,7 @@ __device__ __forceinline__ u32 maybe_send_append(const Groups& pg, u64 g, u64 i,
       n = avail < ments ? avail : ments;
     }
   }
+  if (!SendIfEmpty && n == 0) return 0;
   if (compacted) {
     if (!(st & QB_PR_RECENT_ACTIVE)) return 0;
     const u64 snapi = reinterpret_cast<const u64*>(pg.snap_index)[g];

@@ -30,6 +30,7 @@ from .ready import (AdvanceRecords, AdvanceResult, ReadyResult, ReadyState, adva
                     unstable_truncate)
 from .request import RequestInbox, RequestResult, leader_requests
 from .snapshot import SnapshotInbox, SnapshotResult, follower_snapshot, restored_conf_states
+from .switch import SwitchResult, switch_config
 from .tick import TickResult, TickState, leader_tick
 
 MAX_UINT64 = INDEX_INF
@@ -186,6 +187,6 @@ def vote_results(configs: Sequence[JointConfig], votes: Sequence[Mapping[int, bo
 
 
 __all__ = ["AckedIndexer", "AdvanceRecords", "AdvanceResult", "CampaignResult", "ElectionState", "EncodeGroups", "EncodeOut", "FollowerAppInbox", "FollowerGroups", "FollowerInbox", "FollowerLog", "FollowerLogResult", "FollowerResult", "INDEX_INF",
-           "JointConfig", "MAX_UINT64", "MajorityConfig", "MapAckIndexer", "ProposeInbox", "ProposeResult", "ProposeState", "ReadyResult", "ReadyState", "RequestInbox", "RequestResult", "SnapshotInbox", "SnapshotResult", "TickResult",
+           "JointConfig", "MAX_UINT64", "MajorityConfig", "MapAckIndexer", "ProposeInbox", "ProposeResult", "ProposeState", "ReadyResult", "ReadyState", "RequestInbox", "RequestResult", "SnapshotInbox", "SnapshotResult", "SwitchResult", "TickResult",
            "TickState", "VoteLost", "VotePending", "VoteResult", "VoteWon", "advance", "batch", "campaign", "committed_indexes", "encode_columns", "encode_msg_out", "encode_slots", "follower_log_step", "follower_snapshot", "follower_step", "index_string", "leader_propose", "leader_requests", "leader_tick",
-           "ready", "restored_conf_states", "unstable_truncate", "vote_results"]
+           "ready", "restored_conf_states", "switch_config", "unstable_truncate", "vote_results"]

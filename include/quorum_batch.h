@@ -2373,6 +2373,165 @@ int qb_dev_conf_change(const qb_conf_change_in* in, const qb_conf_change_out* ou
                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* ----------------------------------------------------------------------- */
+/* switchToConfig: what follows a configuration change                     */
+/* ----------------------------------------------------------------------- */
+
+/* raft.switchToConfig (raft.go:1651-1700) for G groups in one call: the tail
+ * of applyConfChange (raft.go:1623-1650) behind qb_dev_conf_change, and the
+ * tail of restore (raft.go:1606-1609) behind qb_dev_follower_snapshot.  Dense,
+ * one action byte per group, groups independent.  The new config and Progress
+ * are qb_dev_conf_change's outputs (off / ids / cfg and the Progress arrays,
+ * read and written in place); old_off / old_ids are the off / ids that went
+ * into that call.
+ *
+ * action[g]:
+ *   QB_SW_NONE     nothing (swflags[g] = 0);
+ *   QB_SW_SWITCH   applyConfChange's tail: steps 1-6;
+ *   QB_SW_RESTORE  restore's tail: steps 1-6, then 7;
+ *   any other code is treated as QB_SW_NONE and counted
+ *   (QB_SWSTAT_BAD_ACTION).
+ *
+ * Per acting group, in this order:
+ *   1. Renumber (this library's representation, not Go; whatever the role).
+ *      A slot is an ID's rank, so the two ascending ID lists give the new
+ *      slot of every old slot (slot_map, 0xFF: removed).  The own slot (meta
+ *      bits 0-7) becomes the rank of self_id in the new IDs, or 0xFF; the
+ *      transferee slot (meta bits 8-15), the ack bits and the From slot of
+ *      each pending rq_meta entry (meta bits 20-24 of them, at most
+ *      readq_cap) and both halves of votes go through the map.  Bits of
+ *      removed slots are dropped.  A dropped voted bit raises
+ *      QB_SWFLAG_VOTE_DROPPED: Go keeps Votes by ID, so this matters only if
+ *      the ID comes back within the same candidacy (the host then records
+ *      that vote again).
+ *   2. Stops, found before anything is written: swflags[g] =
+ *      QB_SWFLAG_HOST alone, nothing of the group changes and no output but
+ *      swflags is written.
+ *      (a) a pending read whose From slot names an ID that is not in the new
+ *          config (Go keeps the message's ID; a slot cannot);
+ *      (b) a leader that is removed or demoted while its transferee's ID is
+ *          not in the new config (Go returns early and keeps the ID).
+ *   3. isLearner: the own slot is present and in neither voter half.  Own
+ *      slot absent or a learner at a leader: QB_SWFLAG_SELF_REMOVED /
+ *      QB_SWFLAG_SELF_LEARNER and 4-6 are skipped (raft.go:1663-1674; the
+ *      transferee is not aborted here, as in Go).
+ *   4. Not a leader, or no incoming voter (cfg & 0xFFFF == 0): 5-6 are
+ *      skipped (raft.go:1678).
+ *   5. maybeCommit (raft.go:585-588, log.go:328-334): the joint committed
+ *      index over the new match and cfg, taken iff it is > committed and its
+ *      term, through the run table, equals term (term() is 0 outside
+ *      [first_index - 1, last_index]).
+ *        true:  QB_SWFLAG_COMMITTED and bcastAppend: maybeSendAppend(to,
+ *               true) for every slot but the own, exactly as
+ *               qb_dev_leader_propose sends;
+ *        false: maybeSendAppend(id, false) for every slot, the own included,
+ *               as Visit does.  With sendIfEmpty == false an empty entry list
+ *               returns before the snapshot fallback (raft.go:442-444), so a
+ *               compacted next sends nothing here.
+ *      Either way QB_SWFLAG_SENT: msg_type[s] = 0 / QB_MSG_APP / QB_MSG_SNAP
+ *      for every new slot of the group, with qb_propose_out's contract
+ *      (Commit is committed[g] after the call).
+ *   6. The transferee, if not 0xFF and in neither voter half of the new
+ *      config, becomes 0xFF: QB_SWFLAG_TRANSFER_ABORTED (raft.go:1695-1697).
+ *   7. QB_SW_RESTORE only, whatever 3 and 4 decided: with an own slot
+ *      present, MaybeUpdate(next - 1) on it (progress.go:144-153).
+ * Every acting group that is not stopped gets QB_SWFLAG_SWITCHED.
+ *
+ * QB_ROLE_PROMOTABLE is not touched: qb_dev_campaign tests membership itself,
+ * the bit carries only !hasPendingSnapshot.  Stays the host's: the ConfState
+ * returned to the application, r.isLearner beyond what meta and cfg say, a
+ * stopped group, and any slot-indexed state of its own (through slot_map).
+ * Index arithmetic wraps as Go's uint64 does.  A slot count above
+ * QB_MAX_SLOTS is read as QB_MAX_SLOTS, a run count of 0 as 1 and above 8 as
+ * 8, a request count above readq_cap as readq_cap; an old slot at or above
+ * the old slot count maps to 0xFF. */
+#define QB_SW_NONE 0
+#define QB_SW_SWITCH 1
+#define QB_SW_RESTORE 2
+
+#define QB_SWFLAG_SWITCHED 0x01u         /* renumbered: meta / votes / rq_meta / slot_map */
+#define QB_SWFLAG_COMMITTED 0x02u        /* maybeCommit returned true               */
+#define QB_SWFLAG_SENT 0x04u             /* step 5 ran: msg_type of the group's slots written */
+#define QB_SWFLAG_TRANSFER_ABORTED 0x08u /* the transferee was removed or demoted   */
+#define QB_SWFLAG_SELF_REMOVED 0x10u     /* a leader without a Progress of its own  */
+#define QB_SWFLAG_SELF_LEARNER 0x20u     /* a leader demoted to learner             */
+#define QB_SWFLAG_VOTE_DROPPED 0x40u     /* a recorded vote's slot was removed      */
+#define QB_SWFLAG_HOST 0x80u             /* stopped: nothing applied                */
+
+enum {
+  QB_SWSTAT_SWITCHED = 0,         /* groups renumbered (restores included)     */
+  QB_SWSTAT_RESTORES = 1,         /* of them under QB_SW_RESTORE               */
+  QB_SWSTAT_COMMITS = 2,
+  QB_SWSTAT_BCAST = 3,            /* groups that ran bcastAppend               */
+  QB_SWSTAT_PROBED = 4,           /* groups that ran maybeSendAppend(id, false) */
+  QB_SWSTAT_MSG_APP = 5,
+  QB_SWSTAT_MSG_SNAP = 6,
+  QB_SWSTAT_TRANSFER_ABORTED = 7,
+  QB_SWSTAT_SELF_REMOVED = 8,
+  QB_SWSTAT_SELF_LEARNER = 9,
+  QB_SWSTAT_VOTE_DROPPED = 10,
+  QB_SWSTAT_HOST = 11,
+  QB_SWSTAT_BAD_ACTION = 12,
+  QB_SWSTAT_COUNT = 13
+};
+
+/* The per-group and Progress arrays are those of qb_leader_groups,
+ * qb_campaign_groups and qb_propose_groups (same layouts: a caller passes the
+ * same buffers), the Progress arrays and off / ids / cfg being
+ * qb_conf_change_out's. */
+typedef struct qb_switch_groups {
+  uint64_t G;
+  uint32_t inflight_cap;        /* 1..4096                                  */
+  uint32_t readq_cap;           /* 0..QB_LEADER_MAX_READQ                   */
+  const uint32_t* old_off;      /* [G+1] the config before the change       */
+  const uint64_t* old_ids;      /* [old_off[G]] ascending per group         */
+  const uint32_t* off;          /* [G+1] the new config                     */
+  const uint64_t* ids;          /* [off[G]] ascending per group             */
+  const uint32_t* cfg;          /* [G] */
+  const uint64_t* self_id;      /* [G] */
+  const uint8_t* role;          /* [G] QB_ROLE_* */
+  const uint64_t* term;         /* [G] */
+  const uint64_t* first_index;  /* [G] */
+  const uint64_t* last_index;   /* [G] */
+  const uint64_t* last_term;    /* [G] the term of last_index */
+  const uint64_t* snap_index;   /* [G] */
+  const uint64_t* snap_term;    /* [G] */
+  const uint64_t* max_ents;     /* [G] */
+  const uint64_t* run_start;    /* [QB_LEADER_MAX_RUNS * G] run-major */
+  const uint64_t* run_term;     /* same layout */
+  uint32_t* meta;               /* [G] in/out: only bits 0-15 may change */
+  uint64_t* committed;          /* [G] in/out */
+  uint32_t* votes;              /* [G] in/out: voted | granted << 16 (nullable) */
+  uint32_t* rq_meta;            /* [G * readq_cap] in/out; NULL iff readq_cap == 0 */
+  /* per new slot, S = off[G] (in/out) */
+  uint64_t* match;
+  uint64_t* next;
+  uint64_t* pending_snapshot;
+  uint8_t* pstate;
+  uint32_t* infl_pos;
+  uint64_t* infl_buf;           /* [S * inflight_cap] */
+} qb_switch_groups;
+
+typedef struct qb_switch_out {
+  uint8_t* swflags;       /* [G] QB_SWFLAG_*, written for every group */
+  uint8_t* slot_map;      /* [old_off[G]] (nullable) the new slot of each old slot, 0xFF:
+                             removed; written for every old slot of a group with
+                             QB_SWFLAG_SWITCHED and for no other slot */
+  uint8_t* msg_type;      /* [S] written for every new slot of a group with QB_SWFLAG_SENT
+                             and for no other slot */
+  uint64_t* msg_index;    /* [S] written only where msg_type != 0 */
+  uint64_t* msg_log_term; /* [S] same */
+  uint64_t* msg_n;        /* [S] same: entries of the MsgApp (0 for a MsgSnap) */
+} qb_switch_out;
+
+/* stats: QB_SWSTAT_COUNT device uint64 (accumulated).  G == 0 is QB_OK and
+ * writes nothing; every pointer but votes, slot_map (and rq_meta with
+ * readq_cap 0) is required.  No workspace and no allocation inside the call
+ * (it can be graph-captured); nothing outside the caller's arrays is read or
+ * written. */
+int qb_dev_switch_config(const qb_switch_groups* sg, const uint8_t* action,
+                         const qb_switch_out* out, uint64_t* stats, void* stream);
+
+/* ----------------------------------------------------------------------- */
 /* Sharding over the GPUs of a node                        */
 /* ----------------------------------------------------------------------- */
 

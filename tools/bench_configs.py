@@ -1746,6 +1746,152 @@ def propose_config(G, reps, *, reporter=None):
     assert ok, "propose parity failed"
 
 
+def switch_config_row(G, reps, *, reporter=None):
+    """The batched switchToConfig (qb_dev_switch_config) at the propose row's
+    G.  Dense: every group a five-voter leader (own slot 0, peers replicating
+    at next = last + 1) that adds one voter whose ID ranks third, so three old
+    slots move; no commit, the new member alone is probed (one MsgApp of one
+    entry, ProbeSent).  Sparse: the same table with one group in a hundred
+    acting.  One HIP event pair per call, median over the samples after
+    warm-up; meta, the new member's pstate and the outputs are restored
+    between samples outside the timed call.  Parity: the dense call's every
+    1024th group against tests/switch_ref.py."""
+    reporter = reporter or report
+    import ctypes as C
+    import importlib
+    import time
+    from etcd_amd import _lib
+    from etcd_amd.quorum import confchange as qcc, switch as qs, tick as qt
+    from etcd_amd.quorum.leader import MAX_RUNS, _to_np, synth_streaming
+    from tests import switch_ref as R
+    qc = importlib.import_module("etcd_amd.quorum.campaign")
+    n0, n, W, D, NEW = 5, 6, 4, 64, 2
+    lg, _ = synth_streaming(G, W=W, D=D, n=n, device=dev)
+    S0, S = n0 * G, lg.S
+    z32 = lambda: torch.zeros(G, dtype=torch.int32, device=dev)  # noqa: E731
+    state = qt.TickState(torch.full((G,), qt.ROLE_LEADER | qt.ROLE_PROMOTABLE, dtype=torch.uint8,
+                                    device=dev), z32(), z32(), z32())
+    lg.t["meta"].fill_(0xFF00 | (1 << 16))  # own slot 0, no transferee, one term run
+    g64 = torch.arange(G, dtype=torch.int64, device=dev)
+    es = qc.ElectionState.for_table(lg, state, (np.arange(G, dtype=np.uint64) * 10 + 1),
+                                    np.zeros(G, np.uint64), np.zeros(G, np.uint64),
+                                    np.full(G, 7, np.uint64), 10, True, True)
+    slot = torch.arange(S, device=dev) % n
+    last = lg.t["last_index"][torch.arange(S, device=dev) // n]
+    fresh = slot == NEW                                     # initProgress: Probe at Next = last
+    lg.t["match"] = torch.where(fresh, 0, torch.where(slot == 0, last, lg.t["match"]))
+    lg.t["next"] = torch.where(fresh, last, last + 1)
+    lg.t["infl_pos"].zero_()
+    pstate0 = torch.where(fresh, 0 | 8, 1 | 8).to(torch.uint8)
+    lg.t["pstate"].copy_(pstate0)
+    ids = (g64[:, None] * 10 + 1 + torch.arange(n, device=dev)[None, :]).reshape(-1)
+    keep = torch.tensor([0, 1, 3, 4, 5], device=dev)
+    old_ids = (g64[:, None] * 10 + 1 + keep[None, :]).reshape(-1)
+    old = qcc.ConfigTable(G, S0, W, {"off": (torch.arange(G + 1, device=dev) * n0).to(torch.int32),
+                                     "ids": old_ids})
+    new = qcc.ConfigTable(G, S, W, dict(lg.t, ids=ids))
+    action = torch.full((G,), qs.SW_SWITCH, dtype=torch.uint8, device=dev)
+    sg, so, out = qs.switch_args(lg, es, old, new, action)   # (the mirror's checks, once)
+    sp = torch.cuda.current_stream(dev).cuda_stream
+    fn = _lib.fn("qb_dev_switch_config")
+    args = (C.byref(sg), action.data_ptr(), C.byref(so), out.stats.data_ptr(), sp)
+    meta0 = lg.t["meta"].clone()
+
+    def timed():
+        def sample(ev):
+            lg.t["meta"].copy_(meta0)
+            lg.t["pstate"].copy_(pstate0)
+            torch.cuda.synchronize()
+            ev.record(ev.ev[0], sp)
+            _lib.check(fn(*args), "qb_dev_switch_config")
+            ev.record(ev.ev[1], sp)
+            torch.cuda.synchronize()
+            return ev.elapsed_ms(0, 1) / 1e3
+        ev = HipEvents(2)
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < 0.3:  # warm-up: clocks settle (time_region)
+            sample(ev)
+        out.stats.zero_()
+        per = [sample(ev) for _ in range(reps)]
+        ev.close()
+        return float(np.median(per)), out.stats_dict()
+    t_dense, st = timed()
+    assert st["switched"] == reps * G and st["probed"] == reps * G and st["msg_app"] == reps * G, st
+    assert st["commits"] == 0 and st["host"] == 0, st
+    # parity of the dense call, every 1024th group
+    sub = np.arange(0, G, 1024)
+    slots = (sub[:, None] * n + np.arange(n)[None, :]).ravel()
+    oslots = (sub[:, None] * n0 + np.arange(n0)[None, :]).ravel()
+    rows = (np.arange(MAX_RUNS)[:, None] * G + sub[None, :]).ravel()
+    ft = es.follower.t
+
+    def gather():
+        a = {k: _to_np(lg.t[k], dt)[sub].copy() for k, dt in (
+            ("cfg", np.uint32), ("meta", np.uint32), ("first_index", np.uint64),
+            ("snap_index", np.uint64), ("snap_term", np.uint64), ("max_ents", np.uint64))}
+        a.update({k: _to_np(ft[k], np.uint64)[sub].copy() for k in ("term", "committed",
+                                                                    "last_index", "last_term")})
+        a.update({k: _to_np(lg.t[k], np.uint64)[rows].copy() for k in ("run_start", "run_term")})
+        a.update({k: _to_np(lg.t[k], dt)[slots].copy() for k, dt in (
+            ("match", np.uint64), ("next", np.uint64), ("pending_snapshot", np.uint64),
+            ("pstate", np.uint8), ("infl_pos", np.uint32))})
+        a["infl_buf"] = _to_np(lg.t["infl_buf"], np.uint64)[
+            (slots[:, None] * W + np.arange(W)[None, :]).ravel()].copy()
+        a["off"] = np.arange(len(sub) + 1, dtype=np.uint32) * n
+        a["old_off"] = np.arange(len(sub) + 1, dtype=np.uint32) * n0
+        a["ids"], a["old_ids"] = _to_np(ids, np.uint64)[slots], _to_np(old_ids, np.uint64)[oslots]
+        a["self_id"] = _to_np(es.self_id, np.uint64)[sub].copy()
+        a["role"] = state.role.cpu().numpy()[sub].copy()
+        a["votes"] = _to_np(es.votes, np.uint32)[sub].copy()
+        a["rq_meta"] = np.zeros(1, np.uint32)
+        return a
+    lg.t["meta"].copy_(meta0)
+    lg.t["pstate"].copy_(pstate0)
+    a0 = gather()
+    fill = R.FILL - (1 << 64)
+    for t_ in (out.swflags, out.slot_map, out.msg_type):
+        t_.fill_(R.FILL8)
+    for t_ in (out.msg_index, out.msg_log_term, out.msg_n):
+        t_.fill_(fill)
+    _lib.check(fn(*args), "qb_dev_switch_config")
+    torch.cuda.synchronize()
+    want = R.new_out(len(sub), len(oslots), len(slots))
+    R.switch_config(a0, np.full(len(sub), R.SW_SWITCH, np.uint8), W, 0, want, R.new_stats())
+    a1 = gather()
+    ok = all(np.array_equal(a1[k], a0[k]) for k in a0)
+    got = {"swflags": out.swflags.cpu().numpy()[sub], "slot_map": out.slot_map.cpu().numpy()[oslots],
+           "msg_type": out.msg_type.cpu().numpy()[slots]}
+    got.update({k: _to_np(getattr(out, k), np.uint64)[slots]
+                for k in ("msg_index", "msg_log_term", "msg_n")})
+    ok = ok and all(np.array_equal(got[k], want[k][:len(got[k])]) for k in got)
+    # sparse: one group in a hundred acts
+    action.copy_(torch.where(g64 % 100 == 0, qs.SW_SWITCH, qs.SW_NONE).to(torch.uint8))
+    t_sparse, st = timed()
+    acting = int((np.arange(G) % 100 == 0).sum())
+    assert st["switched"] == reps * acting and st["msg_app"] == reps * acting, st
+    # per acting group, read: action 1, old_off / off 8, cfg 4, meta 4, role 1,
+    # self_id / term / committed / first / last / last_term / max_ents 56, votes
+    # 4, the ID lists (5 + 6) * 8 = 88, match 6 * 8 = 48; written: swflags 1,
+    # slot_map 5, meta 0 (unchanged) = 220 B.  Per new slot, read: next 8,
+    # pstate 1, infl_pos 4; written: msg_type 1 = 14 B; the new member's
+    # message adds the run row 16 read and msg_* 24, pstate 1 written = 41 B.
+    dense_b = 220 + n * 14 + 41
+    extra = {"unit": "groups/s", "samples": reps, "inflight_cap": W,
+             "dense_us": t_dense * 1e6, "dense_bytes_per_group": dense_b,
+             "dense_TBs": G * dense_b / t_dense / 1e12,
+             "dense_frac": G * dense_b / t_dense / 1e9 / HBM_PEAK_GBS,
+             "sparse_us": t_sparse * 1e6, "sparse_acting_groups": acting,
+             "parity": bool(ok),
+             "parity_check": f"tests/switch_ref.py over {len(sub)} groups (every 1024th) of the "
+                             f"dense call: meta, committed, votes, Progress, rings, swflags, "
+                             f"slot_map and msg_* (untouched elements included)",
+             "timing": "one HIP event pair per call, median over the samples; per_launch_us = "
+                       "the dense case, every group adding one voter to five"}
+    reporter("switch-config (switchToConfig behind an added voter: renumber, maybeCommit, probe)",
+             G, t_dense, G * dense_b, extra)
+    assert ok, "switch-config parity failed"
+
+
 def requests_config(G, reps, *, reporter=None):
     """The batched requests (qb_dev_leader_requests): G five-voter leader groups
     of the synth_streaming table (own slot 0, one term run, committed inside
@@ -2741,6 +2887,8 @@ def main():
         campaign_config(1 << 22, a.reps)
     if "propose" in which:
         propose_config(1 << 22, a.reps)
+    if "switch-config" in which:
+        switch_config_row(1 << 22, a.reps)
     if "requests" in which:
         requests_config(1 << 22, a.reps)
     if "ready" in which:
