@@ -95,6 +95,8 @@ SIGNATURES = {
     "qb_dev_advance": (_i32, [_p, _u64, _p, _p, _p, _p]),
     "qb_dev_unstable_truncate": (_i32, [_u64, _p, _p, _u64, _p, _p]),
     "qb_dev_follower_snapshot": (_i32, [_p, _p, _p, _p, _p]),
+    "qb_log_compact_scratch_bytes": (C.c_size_t, [_u64]),
+    "qb_dev_log_compact": (_i32, [_p, _p, _u64, _p, _p, _p, C.c_size_t, _p]),
     "qb_dev_ingest_messages": (_i32, [_u64, _p, _u64, _p, _p, _u64, _p, _p, _p, _p, _p, _p, _p,
                                       _p, _p, _p, _p, _p]),
     "qb_wire_group_rows_bytes": (C.c_size_t, [_u64]),

@@ -22,6 +22,7 @@ from .batch import INDEX_INF
 # calls are named in the header; the submodules stay importable as
 # etcd_amd.quorum.campaign and etcd_amd.quorum.ready)
 from .campaign import CampaignResult, ElectionState, campaign
+from .compact import CompactRequest, CompactResult, leader_log, log_compact, new_compact_result
 from .encode import EncodeGroups, EncodeOut, encode_columns, encode_msg_out, encode_slots
 from .follower import (FollowerAppInbox, FollowerGroups, FollowerInbox, FollowerLog,
                        FollowerLogResult, FollowerResult, follower_log_step, follower_step)
@@ -186,7 +187,7 @@ def vote_results(configs: Sequence[JointConfig], votes: Sequence[Mapping[int, bo
     return [VoteResult(int(x)) for x in out]
 
 
-__all__ = ["AckedIndexer", "AdvanceRecords", "AdvanceResult", "CampaignResult", "ElectionState", "EncodeGroups", "EncodeOut", "FollowerAppInbox", "FollowerGroups", "FollowerInbox", "FollowerLog", "FollowerLogResult", "FollowerResult", "INDEX_INF",
+__all__ = ["AckedIndexer", "AdvanceRecords", "AdvanceResult", "CampaignResult", "CompactRequest", "CompactResult", "ElectionState", "EncodeGroups", "EncodeOut", "FollowerAppInbox", "FollowerGroups", "FollowerInbox", "FollowerLog", "FollowerLogResult", "FollowerResult", "INDEX_INF",
            "JointConfig", "MAX_UINT64", "MajorityConfig", "MapAckIndexer", "ProposeInbox", "ProposeResult", "ProposeState", "ReadyResult", "ReadyState", "RequestInbox", "RequestResult", "SnapshotInbox", "SnapshotResult", "SwitchResult", "TickResult",
-           "TickState", "VoteLost", "VotePending", "VoteResult", "VoteWon", "advance", "batch", "campaign", "committed_indexes", "encode_columns", "encode_msg_out", "encode_slots", "follower_log_step", "follower_snapshot", "follower_step", "index_string", "leader_propose", "leader_requests", "leader_tick",
+           "TickState", "VoteLost", "VotePending", "VoteResult", "VoteWon", "advance", "batch", "campaign", "committed_indexes", "encode_columns", "encode_msg_out", "encode_slots", "follower_log_step", "follower_snapshot", "follower_step", "index_string", "leader_log", "leader_propose", "leader_requests", "leader_tick", "log_compact", "new_compact_result",
            "ready", "restored_conf_states", "switch_config", "unstable_truncate", "vote_results"]

@@ -931,7 +931,8 @@ int qb_dev_follower_step(const qb_follower_groups* fg, const qb_follower_inbox* 
  *     (unstable.truncateAndAppend's slice bounds) — where a zero LogTerm or
  *     entry term "matching" outside the log ends up;
  *   QB_FFLAG_LOG_RUNS: the table behind the append would hold more than
- *     QB_LEADER_MAX_RUNS runs (the host compacts, or steps the message);
+ *     QB_LEADER_MAX_RUNS runs (the host runs qb_dev_log_compact, or steps the
+ *     message);
  *   QB_FFLAG_COMMIT_RANGE: commitTo's range panic (log.go:239-241) against
  *     the last index the record would leave.
  * Index arithmetic wraps as Go's uint64 does.
@@ -1180,7 +1181,7 @@ int qb_dev_campaign(const qb_campaign_groups* cg, const uint8_t* action, uint8_t
  *      Progress): dropped.
  *   3. the transferee (meta bits 8-15) is not 0xFF: dropped.
  *   4. last_term != term and the table already holds QB_LEADER_MAX_RUNS runs:
- *      QB_PFLAG_LOG_RUNS, nothing applied (the host compacts the table).
+ *      QB_PFLAG_LOG_RUNS, nothing applied (qb_dev_log_compact makes room).
  *   5. the conf-change rule (raft.go:1050-1070): refused iff
  *      pending_conf_index > applied, or joint (cfg >> 16 != 0) without
  *      LEAVE_JOINT, or LEAVE_JOINT while not joint.  Refused:
@@ -1935,6 +1936,184 @@ typedef struct qb_snapshot_out { /* all [R], written for every record */
  * whatever they hold. */
 int qb_dev_follower_snapshot(const qb_snapshot_groups* sg, const qb_snapshot_inbox* in,
                              const qb_snapshot_out* out, uint64_t* stats, void* stream);
+
+/* ----------------------------------------------------------------------- */
+/* Log compaction: CreateSnapshot, Compact and etcdserver's trigger        */
+/* ----------------------------------------------------------------------- */
+
+/* MemoryStorage.CreateSnapshot and Compact (storage.go:190-236) and
+ * etcdserver's policy around them (server/etcdserver/server.go:1096-1117
+ * triggerSnapshot / shouldSnapshot, 1993-2067 snapshot()) for G groups in one
+ * call: what the host runs behind QB_FFLAG_LOG_RUNS and QB_PFLAG_LOG_RUNS, and
+ * the one call that moves snap_index / snap_term and advances first_index on
+ * the node's own account.  The snapshot's data, the WAL and the entries' bytes
+ * stay the host's; the call decides, moves the cursors, shifts the term-run
+ * table and lists the groups that changed.
+ *
+ * The arrays are the other calls' own (same layouts: a caller passes the same
+ * buffers): first_index / meta / run_start / run_term of qb_follower_log and
+ * qb_leader_groups, snap_index / snap_term of qb_leader_groups, and applied /
+ * unstable_offset / usnap_index of qb_ready_groups.
+ *
+ * THE REQUEST, by qb_compact_in::mode.
+ *   QB_CM_EXPLICIT: two independent Storage calls per group, the snapshot
+ *     first: snap_at[g] = CreateSnapshot's i, compact_at[g] = Compact's
+ *     compactIndex, 0 = none; a NULL column is a column of zeros.
+ *   QB_CM_TRIGGER: with snapi = snap_index[g] and appl = applied[g], a group
+ *     triggers iff (force[g] && appl != snapi) || (appl - snapi >
+ *     snapshot_count), the subtraction wrapping as Go's uint64 does
+ *     (shouldSnapshot, server.go:1115-1117; force is forceSnapshot).  A
+ *     triggering group snapshots at appl (server.go:1111), then compacts at
+ *     appl > catch_up_entries ? appl - catch_up_entries : 1
+ *     (server.go:2047-2053).  With hold[g] != 0 (inflightSnapshots != 0,
+ *     server.go:2042-2045) the compaction is skipped behind a snapshot that
+ *     succeeded: QB_CMF_HELD.  A snapshot that does not succeed, for any
+ *     reason, cancels the compaction (snapshot()'s early return,
+ *     server.go:2016-2023).  NULL force / hold are columns of zeros.
+ *
+ * PER GROUP, in this order, with off = first_index - 1 (ms.ents[0].Index) and
+ * stable_last = unstable_offset - 1 (ms.lastIndex(): MemoryStorage holds the
+ * stable entries only):
+ *   1. No request: cmflags[g] = 0; nothing of the group but the request
+ *      columns is read.
+ *   2. first_index == 0, stable_last < off or stable_last > last_index:
+ *      QB_CMF_BAD_LOG, nothing applied.
+ *   3. usnap_index != 0: QB_CMF_PENDING_SNAPSHOT, nothing applied.  A restored
+ *      snapshot has not reached storage yet; the reference's Ready loop
+ *      applies it before triggerSnapshot can run (applyAll,
+ *      server.go:903-915).
+ *   4. Snapshot at s (CreateSnapshot, storage.go:194-213):
+ *        s <= snap_index: QB_CMF_SNAP_OUT_OF_DATE (ErrSnapOutOfDate,
+ *          storage.go:197-199);
+ *        s > stable_last or s < off: QB_CMF_OUT_OF_BOUND (Go panics:
+ *          storage.go:202-204, or the slice index of storage.go:207);
+ *        s > applied: QB_CMF_PAST_APPLIED.  An engine rule: a snapshot is the
+ *          applied state, and etcd only ever passes appliedi;
+ *        else QB_CMF_SNAPPED: snap_index := s, snap_term := term(s) — the term
+ *          of the last run of the table whose start is <= s, run 0 taken to
+ *          start at off.
+ *   5. Compact at c (Compact, storage.go:218-236):
+ *        c <= off: QB_CMF_ALREADY_COMPACTED (ErrCompacted, storage.go:222-224);
+ *        c > stable_last: QB_CMF_OUT_OF_BOUND (storage.go:225-227);
+ *        c > applied: QB_CMF_PAST_APPLIED.  storage.go:216-217 leaves this to
+ *          the application; the table's invariant first_index - 1 <= committed
+ *          needs it;
+ *        else QB_CMF_COMPACTED.  With n runs (meta bits 16-19; 0 is read as 1,
+ *          above QB_LEADER_MAX_RUNS as that) and k the last run whose start is
+ *          <= c (run 0 taken to start at off): new row 0 is (c, run_term[k]),
+ *          new row j is old row k + j for 0 < j < n - k, rows at or above
+ *          n - k keep what they hold, meta bits 16-19 := n - k, first_index :=
+ *          c + 1.  The entry at c becomes the dummy entry, as ents[0] does.
+ *   6. QB_CMF_OUT_OF_BOUND or QB_CMF_PAST_APPLIED from either half: the group
+ *      is not changed at all (Go would not have returned) and carries neither
+ *      QB_CMF_SNAPPED nor QB_CMF_COMPACTED.  QB_CMF_SNAP_OUT_OF_DATE and
+ *      QB_CMF_ALREADY_COMPACTED are plain errors: in explicit mode the other
+ *      half still runs.
+ * Both halves are decided against the state at entry (the snapshot reads the
+ * table before the compaction shifts it).  Index arithmetic wraps as Go's
+ * uint64 does.
+ *
+ * OUTPUTS.  cmflags[g] is written for every group.  The groups with
+ * QB_CMF_SNAPPED or QB_CMF_COMPACTED are listed in ascending group order:
+ * record p (p < min(*list_count, list_cap)) is written in every column —
+ *   gid, flags        the group and its cmflags;
+ *   snap_index, snap_term   the group's snapshot after the call;
+ *   compact_index     c with QB_CMF_COMPACTED, else 0;
+ *   first_before      first_index at entry
+ * — and no record at or past that count is touched.  It is the host's work
+ * list: save the snapshot and release the WAL behind
+ * QB_CMF_SNAPPED, drop the entries below compact_index + 1 behind
+ * QB_CMF_COMPACTED.  *list_count (device) gets the number of such groups,
+ * listed or not.  A group whose position is >= list_cap is deferred:
+ * cmflags[g] |= QB_CMF_DEFERRED, no record, nothing of it applied; the next
+ * call finds it again. */
+#define QB_CM_EXPLICIT 0
+#define QB_CM_TRIGGER 1
+
+#define QB_CMF_SNAPPED 0x0001u           /* snap_index / snap_term moved          */
+#define QB_CMF_COMPACTED 0x0002u         /* first_index and the table moved       */
+#define QB_CMF_SNAP_OUT_OF_DATE 0x0004u  /* ErrSnapOutOfDate                      */
+#define QB_CMF_ALREADY_COMPACTED 0x0008u /* ErrCompacted                          */
+#define QB_CMF_OUT_OF_BOUND 0x0010u      /* stopped: Go panics; nothing applied   */
+#define QB_CMF_PAST_APPLIED 0x0020u      /* stopped: index > applied              */
+#define QB_CMF_HELD 0x0040u              /* trigger: compaction skipped by hold   */
+#define QB_CMF_PENDING_SNAPSHOT 0x0080u  /* usnap_index != 0: nothing applied     */
+#define QB_CMF_BAD_LOG 0x0100u           /* the cursors contradict each other     */
+#define QB_CMF_DEFERRED 0x0200u          /* past list_cap: nothing applied        */
+
+enum {
+  QB_CMSTAT_SNAPPED = 0,          /* groups by flag, over all G groups, deferred ones included */
+  QB_CMSTAT_COMPACTED = 1,
+  QB_CMSTAT_SNAP_OUT_OF_DATE = 2,
+  QB_CMSTAT_ALREADY_COMPACTED = 3,
+  QB_CMSTAT_OUT_OF_BOUND = 4,
+  QB_CMSTAT_PAST_APPLIED = 5,
+  QB_CMSTAT_HELD = 6,
+  QB_CMSTAT_PENDING_SNAPSHOT = 7,
+  QB_CMSTAT_BAD_LOG = 8,
+  QB_CMSTAT_DEFERRED = 9,
+  QB_CMSTAT_LISTED = 10,          /* records written                                  */
+  QB_CMSTAT_ENTRIES_DROPPED = 11, /* sum of c - off over the compactions applied      */
+  QB_CMSTAT_RUNS_DROPPED = 12,    /* sum of k over the compactions applied            */
+  QB_CMSTAT_COUNT = 13
+};
+
+typedef struct qb_compact_groups {
+  uint64_t G;                      /* <= QB_READY_MAX_GROUPS                          */
+  uint64_t* first_index;           /* [G] in/out                                      */
+  uint64_t* snap_index;            /* [G] in/out: qb_leader_groups::snap_index        */
+  uint64_t* snap_term;             /* [G] in/out                                      */
+  uint32_t* meta;                  /* [G] in/out: only bits 16-19 (term runs) may change */
+  uint64_t* run_start;             /* [QB_LEADER_MAX_RUNS * G] run-major, in/out      */
+  uint64_t* run_term;              /* same layout                                     */
+  const uint64_t* last_index;      /* [G]                                             */
+  const uint64_t* applied;         /* [G] qb_ready_groups::applied                    */
+  const uint64_t* unstable_offset; /* [G] qb_ready_groups::unstable_offset            */
+  const uint64_t* usnap_index;     /* [G] qb_ready_groups::usnap_index                */
+} qb_compact_groups;
+
+typedef struct qb_compact_in {
+  uint32_t mode;               /* QB_CM_EXPLICIT / QB_CM_TRIGGER                      */
+  uint32_t reserved;           /* 0                                                   */
+  const uint64_t* snap_at;     /* [G] explicit: CreateSnapshot(i), 0 = none; nullable */
+  const uint64_t* compact_at;  /* [G] explicit: Compact(i), 0 = none; nullable        */
+  uint64_t snapshot_count;     /* trigger: Cfg.SnapshotCount                          */
+  uint64_t catch_up_entries;   /* trigger: Cfg.SnapshotCatchUpEntries                 */
+  const uint8_t* force;        /* [G] trigger: forceSnapshot; nullable                */
+  const uint8_t* hold;         /* [G] trigger: inflightSnapshots != 0; nullable       */
+} qb_compact_in;
+
+typedef struct qb_compact_out {
+  uint16_t* cmflags;       /* [G] QB_CMF_*, written for every group */
+  /* the list, [list_cap] each */
+  uint32_t* gid;
+  uint16_t* flags;
+  uint64_t* snap_index;
+  uint64_t* snap_term;
+  uint64_t* compact_index;
+  uint64_t* first_before;
+  uint64_t* list_count;    /* device, one */
+} qb_compact_out;
+
+/* stats: QB_CMSTAT_COUNT device uint64 (accumulated).  Every pointer is
+ * required but the four request columns (the list's columns too with list_cap
+ * == 0: pass any valid pointer); the columns of the mode not chosen are not
+ * read.  G == 0 is QB_OK and sets *list_count = 0.  A NULL struct, a mode
+ * other than the two, G > QB_READY_MAX_GROUPS (gid is a uint32), a missing
+ * pointer or a workspace below qb_log_compact_scratch_bytes(G) is QB_EINVAL,
+ * found before any HIP call.  No allocation inside the call (it can be
+ * graph-captured); nothing outside the caller's arrays is read or written,
+ * whatever they hold.
+ *
+ * What stays the host's: the snapshot's data and ConfState,
+ * SaveSnap and the WAL release, dropping the entries' bytes, clearing
+ * forceSnapshot, and setting snap_index / snap_term once a restored snapshot
+ * (qb_dev_follower_snapshot) has reached storage — ApplySnapshot
+ * (storage.go:174-188) is not this call. */
+size_t qb_log_compact_scratch_bytes(uint64_t G);
+int qb_dev_log_compact(const qb_compact_groups* cg, const qb_compact_in* in, uint64_t list_cap,
+                       const qb_compact_out* out, uint64_t* stats, void* workspace,
+                       size_t workspace_bytes, void* stream);
 
 /* ----------------------------------------------------------------------- */
 /* Wire ingest                                       */

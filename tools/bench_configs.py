@@ -2840,6 +2840,153 @@ def follower_wire_config(M, reps, *, reporter=None):
     assert ok, "follower wire parity failed"
 
 
+def log_compact_config(G, reps, *, reporter=None):
+    """The batched CreateSnapshot / Compact (qb_dev_log_compact, explicit mode)
+    over G groups.  The call reads no per-slot state, so the voter count of the
+    ready row's five-voter table does not enter; the logs are built here: group
+    g holds n = 1 + g % 8 runs of four entries from the dummy entry at index 0,
+    everything stable and applied, no snapshot yet.  Three samples: no group
+    acting (both request columns zero), every 100th group acting, and every
+    group acting — a snapshot at last_index and a compaction at the second
+    entry of run k, k = (g // 8) % n, so k is spread over 0..7.  One HIP event
+    pair per call, median over the samples after warm-up; the columns the call
+    writes are put back between samples outside the timed call; calls straight
+    to the C ABI.  Bytes: the loads and stores the two kernels issue, summed
+    over the groups of the sample (not a traffic counter).  Parity: behind a
+    dense sample every written column of all G groups against its closed form,
+    and every 1024th group against tests/compact_ref.py."""
+    reporter = reporter or report
+    import ctypes as C
+    import time
+    from etcd_amd import _lib
+    from etcd_amd.quorum import compact as qcm
+    from etcd_amd.quorum._dev import to_np
+    from etcd_amd.quorum.follower import MAX_RUNS, FollowerLog
+    from etcd_amd.quorum.ready import ReadyState
+    from tests import compact_pack as P, compact_ref as R
+    g = torch.arange(G, dtype=torch.int64, device=dev)
+    n = 1 + g % 8
+    q = torch.arange(MAX_RUNS, dtype=torch.int64, device=dev)[:, None]
+    live = q < n[None, :]
+    run_start = torch.where(live, 4 * q, torch.zeros_like(q)).expand(MAX_RUNS, G).contiguous().view(-1)
+    run_term = torch.where(live, q + 1, torch.zeros_like(q)).expand(MAX_RUNS, G).contiguous().view(-1)
+    last = 4 * n - 1
+    k = (g // 8) % n
+    state = {"first_index": torch.ones_like(g), "snap_index": torch.zeros_like(g),
+             "snap_term": torch.zeros_like(g), "meta": (n << 16).to(torch.int32) | 0x0300,
+             "run_start": run_start, "run_term": run_term}
+    saved = {key: v.clone() for key, v in state.items()}
+    log = FollowerLog(G, state["meta"], state["first_index"], state["run_start"], state["run_term"])
+    rdy = ReadyState(G, {"last_index": last, "applied": last.clone(), "unstable_offset": last + 1,
+                         "usnap_index": torch.zeros_like(g)})
+    snap_at, compact_at = torch.zeros_like(g), torch.zeros_like(g)
+    req = qcm.CompactRequest.explicit(snap_at, compact_at)
+    out = qcm.new_compact_result(G, G, dev)
+    qcm.log_compact(log, rdy, state["snap_index"], state["snap_term"], req, out=out)  # (checks, workspace)
+    out.stats.zero_()
+    cg = qcm.CompactGroupsC(G=G, first_index=state["first_index"].data_ptr(),
+                            snap_index=state["snap_index"].data_ptr(),
+                            snap_term=state["snap_term"].data_ptr(), meta=state["meta"].data_ptr(),
+                            run_start=state["run_start"].data_ptr(),
+                            run_term=state["run_term"].data_ptr(),
+                            **{key: rdy.t[key].data_ptr() for key in rdy.t})
+    ci = req.struct()
+    co = qcm.CompactOutC(cmflags=out.cmflags.data_ptr(), list_count=out.list_count.data_ptr(),
+                         **{key: out.cols[key].data_ptr() for key in qcm._LIST})
+    sp = torch.cuda.current_stream(dev).cuda_stream
+    f_compact = _lib.fn("qb_dev_log_compact")
+    ws = out._ws
+
+    def call():
+        _lib.check(f_compact(C.byref(cg), C.byref(ci), G, C.byref(co), out.stats.data_ptr(),
+                             ws.data_ptr(), ws.numel(), sp), "qb_dev_log_compact")
+
+    def restore():
+        for key, v in saved.items():
+            state[key].copy_(v)
+
+    def timed(every):
+        on = (g % every == 0) if every else torch.zeros_like(g, dtype=torch.bool)
+        snap_at.copy_(torch.where(on, last, torch.zeros_like(g)))
+        compact_at.copy_(torch.where(on, 4 * k + 1, torch.zeros_like(g)))
+        Rn = int(on.sum().item())
+
+        def sample(ev):
+            restore()
+            torch.cuda.synchronize()
+            ev.record(ev.ev[0], sp)
+            call()
+            ev.record(ev.ev[1], sp)
+            torch.cuda.synchronize()
+            return ev.elapsed_ms(0, 1) / 1e3
+        ev = HipEvents(2)
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < 0.3:  # warm-up: clocks settle (time_region)
+            sample(ev)
+        out.stats.zero_()
+        per = [sample(ev) for _ in range(reps)]
+        ev.close()
+        st = out.stats_dict()
+        assert int(out.list_count.cpu()[0]) == Rn, (every, Rn)
+        assert st["snapped"] == st["compacted"] == st["listed"] == reps * Rn, st
+        assert st["runs_dropped"] == reps * int(k[on].sum().item()), st
+        # C1: the two request columns read, cmflags written; an acting group's
+        # six cursor words.  C2: cmflags read; per listed group the request 16,
+        # first_index 8 and meta 4 read, n rows of 16 read, the snapshot 16, the
+        # kept rows (16 each; with k == 0 row 0's start alone), meta 4 (when the
+        # count moves) and first_index 8 written, the record 46.
+        nk = (n - k)[on]
+        rows_w = torch.where(k[on] == 0, torch.full_like(nk, 8), 16 * nk)
+        b = G * (16 + 2 + 2) + Rn * (48 + 28 + 16 + 8 + 46) + int((16 * n[on]).sum().item()) + int(
+            rows_w.sum().item()) + 4 * int((k[on] != 0).sum().item())
+        return float(np.median(per)), Rn, b
+
+    rows = {}
+    for name, every in (("idle", 0), ("one_percent", 100), ("dense", 1)):
+        t, Rn, b = timed(every)
+        rows[name] = {"acting_groups": Rn, "us": t * 1e6, "bytes": b, "bytes_per_group": b / G,
+                      "TBs": b / t / 1e12, "frac": b / t / 1e9 / HBM_PEAK_GBS}
+
+    # ---- parity behind the dense sample ---------------------------------
+    c = 4 * k + 1
+    assert bool((state["first_index"] == c + 1).all()) and bool((state["snap_index"] == last).all())
+    assert bool((state["snap_term"] == n).all())
+    assert bool((state["meta"] == (((n - k) << 16).to(torch.int32) | 0x0300)).all())
+    rs, rt = state["run_start"].view(MAX_RUNS, G), state["run_term"].view(MAX_RUNS, G)
+    kept = q < (n - k)[None, :]
+    want_rs = torch.where(q == 0, c[None, :], 4 * (q + k[None, :]))
+    assert bool((rs == torch.where(kept, want_rs, saved["run_start"].view(MAX_RUNS, G))).all())
+    assert bool((rt == torch.where(kept, q + k[None, :] + 1, saved["run_term"].view(MAX_RUNS, G))).all())
+    assert bool((out.cols["gid"] == g.to(torch.int32)).all())
+    assert bool((out.cols["compact_index"] == c).all()) and bool((out.cols["first_before"] == 1).all())
+    pick = torch.arange(0, G, 1024, device=dev)
+    cols = {"first_index": state["first_index"], "snap_index": state["snap_index"],
+            "snap_term": state["snap_term"], "meta": state["meta"], **rdy.t}
+    got = {key: to_np(cols[key][pick], P.STATE[key]) for key in cols}
+    got["run_start"], got["run_term"] = (to_np(x[:, pick].contiguous(), np.uint64) for x in (rs, rt))
+    before = {key: to_np(saved[key][pick], P.STATE[key]) for key in ("first_index", "snap_index",
+                                                                      "snap_term", "meta")}
+    before["run_start"], before["run_term"] = (
+        to_np(saved[key].view(MAX_RUNS, G)[:, pick].contiguous(), np.uint64)
+        for key in ("run_start", "run_term"))
+    before.update({key: got[key] for key in rdy.t})
+    nodes = P.unpack_nodes(before)
+    ref = R.log_compact(nodes, R.Request(R.CM_EXPLICIT, snap_at=to_np(last[pick], np.uint64),
+                                         compact_at=to_np(c[pick], np.uint64)), len(nodes),
+                        R.new_stats())
+    want = P.pack_nodes(nodes, base=before)
+    assert all(f == (R.SNAPPED | R.COMPACTED) for f in ref.flags)
+    for key in P.STATE:
+        assert np.array_equal(got[key].reshape(-1), want[key].reshape(-1)), key
+    d = rows["dense"]
+    reporter("log_compact", G, d["us"] / 1e6, d["bytes"],
+             {"unit": "groups/s", "samples": reps,
+              "timing": "one HIP event pair around qb_dev_log_compact, median over the samples; "
+                        "per_launch_us is the dense sample",
+              "parity": "all groups against the closed form, every 1024th against compact_ref",
+              **{f"{name}_{f}": v for name, r in rows.items() for f, v in r.items()}})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -2895,6 +3042,8 @@ def main():
         ready_config(1 << 22, a.reps)
     if "snapshot" in which:
         snapshot_config(1 << 22, a.reps)
+    if "log-compact" in which:
+        log_compact_config(1 << 22, a.reps)
     if "encode" in which:
         encode_config(1 << 22, a.reps)
     if "follower-wire" in which:
