@@ -111,6 +111,9 @@ SIGNATURES = {
                                        [C.c_size_t, _p]),
     "qb_wire_follower_scratch_bytes": (C.c_size_t, [_u64]),
     "qb_dev_ingest_follower": (_i32, [_u64, _p, _u64, _p, _p, _u64, _p, _p, C.c_size_t, _p]),
+    "qb_wire_requests_scratch_bytes": (C.c_size_t, [_u64, _u64]),
+    "qb_dev_ingest_requests": (_i32, [_u64, _p, _u64, _p, _p, _u64, _p, _p, _u32, _u32, _p, _p,
+                                      C.c_size_t, _p]),
     "qb_encode_scratch_bytes": (C.c_size_t, [_u64]),
     "qb_dev_encode_messages": (_i32, [_u64, _p, _p, _p, C.c_size_t, _p]),
     "qb_dev_encode_msg_out": (_i32, [_p, _p, _u64, _p, _p, _p, C.c_size_t, _p]),

@@ -192,6 +192,15 @@ struct NoSink {};
 // allocation of the leader ingest's deferred launch, though it emits no code)
 template <class Sink>
 constexpr bool kHasSink = !std::is_same<Sink, NoSink>::value;
+// A Sink that declares `static constexpr bool kWantsBody = true` also has
+// e_type, e_data_pos and e_data_len, filled from the Entry's Type (1) and the
+// byte range of its Data (4) — 0 where the field is absent, the last one where
+// it repeats (qb_wire_requests.hip: the conf-change entries of a MsgProp and
+// the request id of a MsgReadIndex).  Data is still never read here.
+template <class Sink, class = void>
+constexpr bool kSinkBody = false;
+template <class Sink>
+constexpr bool kSinkBody<Sink, std::enable_if_t<Sink::kWantsBody>> = true;
 
 // The generated Unmarshal of one message kind on [i, l): nested bodies are
 // decoded by the nested kind's own instantiation (the nesting is fixed:
@@ -212,7 +221,14 @@ __device__ __forceinline__ bool unmarshal(const Src& s, u64 i, const u64 l, Fiel
     const u32 ft = field_type(KIND, fnum, &nested);
     if (ft == T_UNKNOWN) {
       i = pre;
-      if (!skip_field(s, i, l)) return false;
+      // (a kWantsBody decoder has the conf-change decoders beside it: past
+      // that size the compiler stops inlining skip_field by itself, and a
+      // called skip_field keeps the position in scratch)
+      if constexpr (kSinkBody<Sink>) {
+        if (!skip_field_body(s, i, l)) return false;
+      } else {
+        if (!skip_field(s, i, l)) return false;
+      }
       continue;
     }
     if (ft == T_VARINT || (ft == T_REPEATED && wt == 0)) {
@@ -238,6 +254,9 @@ __device__ __forceinline__ bool unmarshal(const Src& s, u64 i, const u64 l, Fiel
         if (fnum == 2) sink->e_term = v;
         if (fnum == 3) sink->e_index = v;
       }
+      if constexpr (KIND == K_ENTRY && kSinkBody<Sink>) {
+        if (fnum == 1) sink->e_type = v;
+      }
       continue;
     }
     if (wt != 2) return false;  // wrong wiretype
@@ -254,6 +273,10 @@ __device__ __forceinline__ bool unmarshal(const Src& s, u64 i, const u64 l, Fiel
           f->ctx_len = len;
         }
       }
+      if constexpr (KIND == K_ENTRY && kSinkBody<Sink>) {  // (Data: an Entry's only bytes field)
+        sink->e_data_pos = i;
+        sink->e_data_len = len;
+      }
       i = post;
     } else if (ft == T_REPEATED) {  // packed: each varint bounded by l, not post
       while (i < post) {
@@ -266,6 +289,7 @@ __device__ __forceinline__ bool unmarshal(const Src& s, u64 i, const u64 l, Fiel
         if (nested == K_ENTRY) {
           sink->e_term = 0;
           sink->e_index = 0;
+          if constexpr (kSinkBody<Sink>) sink->e_type = sink->e_data_pos = sink->e_data_len = 0;
           ok = unmarshal<K_ENTRY>(s, i, post, nullptr, sink);
           if (ok) sink->entry(pre, post);
         } else {

@@ -33,6 +33,7 @@ from .request import RequestInbox, RequestResult, leader_requests
 from .snapshot import SnapshotInbox, SnapshotResult, follower_snapshot, restored_conf_states
 from .switch import SwitchResult, switch_config
 from .tick import TickResult, TickState, leader_tick
+from .wire import RequestIngest, ingest_requests
 
 MAX_UINT64 = INDEX_INF
 
@@ -188,6 +189,6 @@ def vote_results(configs: Sequence[JointConfig], votes: Sequence[Mapping[int, bo
 
 
 __all__ = ["AckedIndexer", "AdvanceRecords", "AdvanceResult", "CampaignResult", "CompactRequest", "CompactResult", "ElectionState", "EncodeGroups", "EncodeOut", "FollowerAppInbox", "FollowerGroups", "FollowerInbox", "FollowerLog", "FollowerLogResult", "FollowerResult", "INDEX_INF",
-           "JointConfig", "MAX_UINT64", "MajorityConfig", "MapAckIndexer", "ProposeInbox", "ProposeResult", "ProposeState", "ReadyResult", "ReadyState", "RequestInbox", "RequestResult", "SnapshotInbox", "SnapshotResult", "SwitchResult", "TickResult",
-           "TickState", "VoteLost", "VotePending", "VoteResult", "VoteWon", "advance", "batch", "campaign", "committed_indexes", "encode_columns", "encode_msg_out", "encode_slots", "follower_log_step", "follower_snapshot", "follower_step", "index_string", "leader_log", "leader_propose", "leader_requests", "leader_tick", "log_compact", "new_compact_result",
+           "JointConfig", "MAX_UINT64", "MajorityConfig", "MapAckIndexer", "ProposeInbox", "ProposeResult", "ProposeState", "ReadyResult", "ReadyState", "RequestInbox", "RequestIngest", "RequestResult", "SnapshotInbox", "SnapshotResult", "SwitchResult", "TickResult",
+           "TickState", "VoteLost", "VotePending", "VoteResult", "VoteWon", "advance", "batch", "campaign", "committed_indexes", "encode_columns", "encode_msg_out", "encode_slots", "follower_log_step", "follower_snapshot", "follower_step", "index_string", "ingest_requests", "leader_log", "leader_propose", "leader_requests", "leader_tick", "log_compact", "new_compact_result",
            "ready", "restored_conf_states", "switch_config", "unstable_truncate", "vote_results"]

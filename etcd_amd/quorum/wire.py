@@ -256,6 +256,136 @@ def ingest_follower(buf: torch.Tensor, nbytes: int, msg_off: torch.Tensor, msg_g
                       ent_bytes=o.ent_bytes[:M], ent_n=o.ent_n[:M])
 
 
+# ------------------------------------------------------ request ingest ---
+
+WIRE_TERM, WIRE_CONF_CHANGE, WIRE_GROUP, WIRE_DEFERRED = 6, 7, 8, 9  # ingest_requests only
+RQ_NONE, RQ_PROP, RQ_READ, RQ_TRANSFER, RQ_READ_RESP = range(5)
+RWFLAG_TAKEN, RWFLAG_DEFERRED = 1, 2
+NO_CONF_CHANGE = 0xFFFFFFFF  # cc_at of a MsgProp without one
+SLOT_LOCAL, SLOT_NONE = 0xFF, 0xFE
+WIRE_REQUEST_STAT_NAMES = ("ok", "unmarshal", "type", "ctx", "entries", "no_space", "term",
+                           "conf_change", "group", "deferred", "taken_props", "taken_reads",
+                           "taken_transfers", "read_resps", "entries_taken")
+
+# (field, dtype) of struct qb_request_wire_out, in order: the message-aligned
+# columns [M], then the dense ones
+_RW_MSG = (("kind", torch.uint8), ("status", torch.uint8), ("group", torch.int32),
+           ("from", torch.int64), ("term", torch.int64), ("msg_type", torch.uint8),
+           ("slot", torch.uint8), ("ctx", torch.int64), ("index", torch.int64),
+           ("ent_n", torch.int32), ("payload", torch.int64), ("ent_pos", torch.int64),
+           ("ent_bytes", torch.int32), ("cc_at", torch.int32), ("cc_payload", torch.int64),
+           ("cc_leave", torch.uint8), ("rd_k", torch.uint8), ("ent_base", torch.int32))
+_RW_DENSE = (("n_reads", torch.uint8, 0), ("rd_ctx", torch.int64, 1), ("rd_from", torch.uint8, 1),
+             ("xf_from", torch.uint8, 0), ("xf_term", torch.int64, 0), ("action", torch.uint8, 0),
+             ("n_ents", torch.int32, 0), ("g_payload", torch.int64, 0), ("g_cc_at", torch.int32, 0),
+             ("g_cc_payload", torch.int64, 0), ("gflags", torch.uint8, 0))
+
+
+class RequestWireOutC(C.Structure):
+    """struct qb_request_wire_out (include/quorum_batch.h)."""
+    _fields_ = [(n, C.c_void_p) for n, _ in _RW_MSG] + [(n, C.c_void_p) for n, _, _ in _RW_DENSE] + \
+        [("stats", C.c_void_p)]
+
+
+class RequestIngest(NamedTuple):
+    """What ``ingest_requests`` returns: the message-aligned columns ([M];
+    ``frm`` is the struct's ``from``), the inboxes the two dense calls take as
+    they are — ``request_in`` first, ``propose_in`` second — and ``gflags``."""
+    kind: torch.Tensor        # uint8 RQ_*
+    status: torch.Tensor      # uint8 WIRE_*
+    group: torch.Tensor       # int32
+    frm: torch.Tensor         # int64
+    term: torch.Tensor        # int64
+    msg_type: torch.Tensor    # uint8 the low byte of Message.Type
+    slot: torch.Tensor        # uint8 READ / TRANSFER: From's slot, SLOT_LOCAL, SLOT_NONE
+    ctx: torch.Tensor         # int64 READ / READ_RESP
+    index: torch.Tensor       # int64 READ_RESP
+    ent_n: torch.Tensor       # int32 PROP
+    payload: torch.Tensor     # int64 PROP
+    ent_pos: torch.Tensor     # int64 PROP: the entries' byte range inside buf
+    ent_bytes: torch.Tensor   # int32 PROP
+    cc_at: torch.Tensor       # int32 PROP: NO_CONF_CHANGE (-1 as stored) = none
+    cc_payload: torch.Tensor  # int64 PROP
+    cc_leave: torch.Tensor    # uint8 PROP
+    rd_k: torch.Tensor        # uint8 a taken READ's row
+    ent_base: torch.Tensor    # int32 a taken PROP's first entry within n_ents[g]
+    request_in: "RequestInbox"
+    propose_in: "ProposeInbox"
+    gflags: torch.Tensor      # uint8 [G] RWFLAG_*
+
+
+_request_ws = {}
+
+
+def new_request_out(M: int, G: int, max_reads: int, device) -> RequestIngest:
+    """Fresh output tensors of ``ingest_requests`` (never empty, so every
+    pointer is valid)."""
+    from .propose import ProposeInbox
+    from .request import RequestInbox
+    n, g = max(M, 1), max(G, 1)
+    e = lambda k, dt: torch.empty(k, dtype=dt, device=device)  # noqa: E731
+    msg = [e(n, dt) for _, dt in _RW_MSG]
+    d = {name: e(g * (max_reads if per_read else 1), dt) for name, dt, per_read in _RW_DENSE}
+    rin = RequestInbox(max_reads, d["n_reads"], d["rd_ctx"], d["rd_from"], d["xf_from"], d["xf_term"])
+    pin = ProposeInbox(d["action"], d["n_ents"], d["g_payload"], d["g_cc_at"], d["g_cc_payload"])
+    return RequestIngest(*msg, rin, pin, d["gflags"])
+
+
+def ingest_requests(buf: torch.Tensor, nbytes: int, msg_off: torch.Tensor, msg_group: torch.Tensor,
+                    off: torch.Tensor, ids: torch.Tensor, *, max_reads: int = 1, concat: bool = False,
+                    stats: torch.Tensor = None, out: Optional[RequestIngest] = None,
+                    stream=None) -> RequestIngest:
+    """Decode M = len(msg_group) request messages at the leaders of G =
+    len(off) - 1 groups (qb_dev_ingest_requests): MsgProp, MsgReadIndex and
+    MsgTransferLeader become the dense inputs of ``leader_requests``
+    (``.request_in``, run first) and ``leader_propose`` (``.propose_in``, run
+    second); MsgReadIndexResp is decoded for the host.  ``off`` / ``ids`` are
+    the groups' CSR slot IDs as for ``ingest``.  ``max_reads`` reads per group
+    and call are taken; ``concat`` concatenates a group's proposals into one
+    (False: one MsgProp per group and call).  A message behind what the call
+    took has status WIRE_DEFERRED and is submitted again.  ``stats`` (int64
+    [15], nullable) accumulates WIRE_REQUEST_STAT_NAMES.  ``out`` (a
+    ``RequestIngest`` of the caller's tensors) is written in place of fresh
+    tensors and returned as it is."""
+    from .request import MAX_READS
+    _check_batch(buf, nbytes, msg_off, msg_group)
+    _check_tensors(((buf, "buf", (torch.uint8,), 0), (off, "off", (torch.int32,), 1),
+                    (ids, "ids", (torch.int64,), 0),
+                    (stats, "stats", (torch.int64,), len(WIRE_REQUEST_STAT_NAMES))))
+    if not isinstance(max_reads, int) or not 1 <= max_reads <= MAX_READS:
+        raise _lib.QuorumBatchError(f"max_reads must be 1..{MAX_READS}, got {max_reads!r}")
+    M, G = msg_group.numel(), off.numel() - 1
+    if M > 0xFFFFFFFE or nbytes >= 1 << 32:
+        raise _lib.QuorumBatchError(f"batch of {M} messages / {nbytes} bytes too large for one call "
+                                    "(M <= 2^32 - 2, nbytes < 2^32)")
+    dev = buf.device
+    o = new_request_out(M, G, max_reads, dev) if out is None else out
+    rin, pin = o.request_in, o.propose_in
+    if rin.max_reads != max_reads:
+        raise _lib.QuorumBatchError(f"out.request_in has max_reads {rin.max_reads}, the call {max_reads}")
+    dense = {"n_reads": rin.n_reads, "rd_ctx": rin.rd_ctx, "rd_from": rin.rd_from,
+             "xf_from": rin.xf_from, "xf_term": rin.xf_term, "action": pin.action,
+             "n_ents": pin.n_ents, "g_payload": pin.payload, "g_cc_at": pin.cc_at,
+             "g_cc_payload": pin.cc_payload, "gflags": o.gflags}
+    cols = [(getattr(o, "frm" if name == "from" else name), name, dt, M) for name, dt in _RW_MSG] + \
+        [(dense[name], name, dt, G * (max_reads if per_read else 1)) for name, dt, per_read in _RW_DENSE]
+    for t, name, _, _ in cols:
+        if t is None:
+            raise _lib.QuorumBatchError(f"ingest_requests out: {name} is missing")
+    _check_tensors(((buf, "buf", (torch.uint8,), 0),) + tuple((t, name, (dt,), n) for t, name, dt, n in cols))
+    need = int(_lib.fn("qb_wire_requests_scratch_bytes")(G, M))
+    key = (dev, stream_handle(dev, stream))  # one workspace per stream: calls on two may overlap
+    ws = _request_ws[key] = grow_workspace(_request_ws.get(key), need, dev)
+    c = RequestWireOutC(*[t.data_ptr() for t, _, _, _ in cols], None if stats is None else stats.data_ptr())
+    _lib.call("qb_dev_ingest_requests", M, buf.data_ptr(), nbytes, msg_off.data_ptr(),
+              msg_group.data_ptr(), G, off.data_ptr(), ids.data_ptr(), max_reads, 1 if concat else 0,
+              C.byref(c), ws.data_ptr(), ws.numel(), key[1])
+    if out is not None:
+        return out
+    fields = ["frm" if name == "from" else name for name, _ in _RW_MSG]
+    return o._replace(**{k: getattr(o, k)[:M] for k in fields})
+
+
 # ------------------------------------------------------- workload synth ---
 
 def _vfix(v: np.ndarray, n: int) -> np.ndarray:

@@ -2317,6 +2317,177 @@ int qb_dev_ingest_follower(uint64_t M, const uint8_t* bytes, uint64_t nbytes,
                            const qb_follower_wire_out* out, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* The requests' ingest: raw raftpb.Message bytes -> the dense inputs of
+ * qb_dev_leader_requests (qb_request_in) and qb_dev_leader_propose
+ * (qb_propose_in), with no host pass between them.  These are the messages a
+ * leader receives for its followers' clients — a forwarded MsgProp
+ * (raft.go:1423-1433), MsgReadIndex and MsgTransferLeader (raft.go:1458-1470) —
+ * and the MsgReadIndexResp a follower gets back.  bytes, nbytes, msg_off
+ * [M+1], msg_group [M], off [G+1], ids and the validation (Message.Unmarshal,
+ * raftpb/raft.pb.go:1739-2061, Entry.Unmarshal 1360-1500, skipRaft) are
+ * qb_dev_ingest_messages'.  Classification goes by Message.Type as Go holds
+ * it, an int32 (the varint's low 32 bits).
+ *
+ * Pass 1, per message i: kind[i], status[i], group[i] = msg_group[i], from[i],
+ * term[i] (as sent) and msg_type[i] (the low byte), plus the kind's own
+ * columns; every column a kind does not name is 0.
+ *   does not unmarshal, or the slice is not inside the buffer:
+ *     QB_WIRE_UNMARSHAL, QB_RQ_NONE; group = UINT32_MAX, every other column 0.
+ *   MsgProp (2): QB_RQ_PROP.  ent_n = the number of field-7 fields, payload =
+ *     the sum of len(Entry.Data) (PayloadSize, util.go:160; a nil Data counts
+ *     0; Data is skipped by its length and read only where it is a conf
+ *     change), ent_pos / ent_bytes = the byte range of the field-7 fields
+ *     inside bytes where they are one contiguous range (the mirror of the
+ *     follower ingest's; 0 / 0 otherwise).  Entry.Index and Entry.Term are
+ *     validated and ignored: appendEntry overwrites them (raft.go:621-628).
+ *     An entry of Type 1 (EntryConfChange) has its Data validated as
+ *     ConfChange.Unmarshal, one of Type 2 (EntryConfChangeV2) as
+ *     ConfChangeV2.Unmarshal (raft.pb.go:2543-2908).  cc_at = that entry's
+ *     0-based position (UINT32_MAX: the message carries no conf change),
+ *     cc_payload = its Data length, cc_leave = 1 iff it is a V2 without a
+ *     field 2 (len(cc.AsV2().Changes) == 0, raft.go:1053; a V1 always has one
+ *     change, so an empty V1 Data is not a leave).  In this order:
+ *       Message.Term != 0: QB_WIRE_TERM (raft.send never puts a term on
+ *         MsgProp or MsgReadIndex, raft.go:402-416; Step's term filter would
+ *         act on one, so the message is the host's);
+ *       no entries, or another field between two entries: QB_WIRE_ENTRIES;
+ *       a conf-change Data that does not unmarshal (Go panics,
+ *         raft.go:1039-1047) or a second conf-change entry:
+ *         QB_WIRE_CONF_CHANGE, cc_at = UINT32_MAX, cc_payload = cc_leave = 0.
+ *   MsgReadIndex (15): QB_RQ_READ.  The request's only field-7 entry must
+ *     carry 8 bytes of Data that are not all zero: ctx = that id, big-endian.
+ *     slot = From's slot among ids[off[g] .. off[g+1]) (at most QB_MAX_SLOTS
+ *     of them): From == 0 gives 0xFF, a local request; a non-member 0xFE,
+ *     which qb_dev_leader_requests answers QB_RD_HOST.  Term != 0:
+ *     QB_WIRE_TERM; else no entry, two entries or another Data: QB_WIRE_CTX
+ *     (ctx = 0).  Message.Context is ignored, as stepLeader ignores it.
+ *   MsgTransferLeader (13): QB_RQ_TRANSFER.  slot = From's slot, 0xFE for a
+ *     non-member (From == 0 included: "no Progress", ignored by the step);
+ *     term is Message.Term as sent: the step has the filter.
+ *   MsgReadIndexResp (16): QB_RQ_READ_RESP, decoded only: index = Index, ctx
+ *     as for the read (another shape: QB_WIRE_CTX).  STEPPING IT IS THE
+ *     HOST'S: the term filter on term[i] and one ReadState{index, ctx} append
+ *     (raft.go:1465-1470).  It takes no part in pass 2 and no group check.
+ *   every other type: QB_WIRE_TYPE, QB_RQ_NONE.
+ *   a message of kinds 1-3 still QB_WIRE_OK whose msg_group[i] >= G:
+ *     QB_WIRE_GROUP (the dense columns have no place for it; slot is 0xFE
+ *     unless the read is local).
+ *
+ * Pass 2, per group: its messages of kinds 1-3 with status QB_WIRE_OK are
+ * walked in batch order, whatever the skew (one group may hold the whole
+ * batch).  A message is TAKEN into the dense columns unless a rule defers it:
+ *   QB_RQ_READ      max_reads reads of the group are already taken, or a
+ *                   proposal is;
+ *   QB_RQ_TRANSFER  a transfer is already taken, or a proposal is;
+ *   QB_RQ_PROP      a proposal is already taken and concat == 0; with concat
+ *                   != 0: it carries a conf change and a taken one already
+ *                   does, or the entry count would pass 2^32 - 1.
+ * Once one message of a group is deferred every later one of that group is
+ * too, which keeps arrival order across calls.  A deferred message gets
+ * status QB_WIRE_DEFERRED and changes no dense column; its other columns stay,
+ * and the host submits it again as it is.  concat == 0 gives one MsgProp per
+ * group and call, Step's own granularity; concat != 0 the concatenation of a
+ * group's proposals into one.
+ *
+ * THE HOST RUNS qb_dev_leader_requests FIRST AND qb_dev_leader_propose SECOND
+ * on these columns.  That fixed order is what makes the two dense calls equal
+ * to stepping the taken messages one by one: reads and the transfer commute
+ * (see qb_dev_leader_requests), but a proposal can move `committed` in a
+ * one-voter group, which a read queued behind it would see — so a read or
+ * transfer behind a taken proposal waits for the next call.
+ *
+ * Per taken message: rd_k[i] = the read's row, ent_base[i] = the entries of
+ * the group's proposal before this message's (its entries get the indexes
+ * last_index - n_ents + 1 + ent_base[i] .. once QB_PFLAG_APPENDED comes back);
+ * both are 0 for every other message.  Dense outputs, written for every group
+ * (the caller zeroes nothing): n_reads[g]; rd_ctx / rd_from[k * G + g] for k <
+ * n_reads[g] only; xf_from[g] (0xFF: none) and xf_term[g]; action[g] =
+ * QB_PROP_NONE, or QB_PROP_ENTRIES with QB_PROP_CONF_CHANGE /
+ * QB_PROP_CC_LEAVE_JOINT; n_ents[g] and g_payload[g], the sums; g_cc_at[g] =
+ * the taken message's ent_base + its cc_at, g_cc_payload[g]; gflags[g] =
+ * QB_RWFLAG_*.  These are exactly qb_request_in {n_reads, rd_ctx, rd_from,
+ * xf_from, xf_term} and qb_propose_in {action, n_ents, g_payload, g_cc_at,
+ * g_cc_payload}: a caller passes them on untouched.
+ *
+ * stats (nullable, QB_RWSTAT_COUNT device uint64, accumulated): one counter
+ * per final status at its QB_WIRE_* value, then the QB_RWSTAT_* ones.
+ *
+ * qb_wire_requests_scratch_bytes(G, M) is 0 for G or M > 2^32 - 2.  A NULL
+ * out, max_reads outside 1..QB_REQ_MAX_READS; with G > 0 a NULL off, ids or
+ * dense output; with M > 0 a NULL msg_off, msg_group, message column or bytes
+ * with nbytes > 0; a short workspace, such an M or G, or nbytes >= 2^32 is
+ * QB_EINVAL before any launch (stats alone is nullable).  G == 0 is QB_OK and
+ * writes nothing; M == 0 with G > 0 still writes the dense columns.  No
+ * allocation inside the call (it can be graph-captured); nothing outside
+ * [bytes, bytes + nbytes) is read and nothing outside the caller's arrays
+ * written, whatever off / ids hold. */
+#define QB_WIRE_TERM 6        /* MsgProp / MsgReadIndex with a Term             */
+#define QB_WIRE_CONF_CHANGE 7 /* conf change that does not unmarshal, or two    */
+#define QB_WIRE_GROUP 8       /* msg_group >= G                                 */
+#define QB_WIRE_DEFERRED 9    /* submit again: behind what this call took       */
+
+#define QB_RQ_NONE 0
+#define QB_RQ_PROP 1
+#define QB_RQ_READ 2
+#define QB_RQ_TRANSFER 3
+#define QB_RQ_READ_RESP 4
+
+#define QB_RWFLAG_TAKEN 0x01u    /* a message of the group went into the dense columns */
+#define QB_RWFLAG_DEFERRED 0x02u /* a message of the group was deferred                */
+
+enum {
+  /* 0 .. 9: the final statuses, at their QB_WIRE_* values (5 stays 0) */
+  QB_RWSTAT_TAKEN_PROPS = 10,
+  QB_RWSTAT_TAKEN_READS = 11,
+  QB_RWSTAT_TAKEN_TRANSFERS = 12,
+  QB_RWSTAT_READ_RESPS = 13,     /* QB_RQ_READ_RESP with QB_WIRE_OK           */
+  QB_RWSTAT_ENTRIES_TAKEN = 14,  /* the sum of n_ents                         */
+  QB_RWSTAT_COUNT = 15
+};
+
+typedef struct qb_request_wire_out {
+  /* message-aligned, [M] */
+  uint8_t* kind;          /* QB_RQ_*                                          */
+  uint8_t* status;        /* QB_WIRE_*                                        */
+  uint32_t* group;
+  uint64_t* from;
+  uint64_t* term;
+  uint8_t* msg_type;      /* the low byte of Message.Type                     */
+  uint8_t* slot;          /* READ / TRANSFER: From's slot, 0xFF local, 0xFE none */
+  uint64_t* ctx;          /* READ / READ_RESP: the request id                 */
+  uint64_t* index;        /* READ_RESP: Message.Index                         */
+  uint32_t* ent_n;        /* PROP                                             */
+  uint64_t* payload;      /* PROP                                             */
+  uint64_t* ent_pos;      /* PROP                                             */
+  uint32_t* ent_bytes;    /* PROP                                             */
+  uint32_t* cc_at;        /* PROP: UINT32_MAX = no conf change                */
+  uint64_t* cc_payload;   /* PROP                                             */
+  uint8_t* cc_leave;      /* PROP                                             */
+  uint8_t* rd_k;          /* a taken READ's row                               */
+  uint32_t* ent_base;     /* a taken PROP's first entry within n_ents[g]      */
+  /* dense: qb_request_in */
+  uint8_t* n_reads;       /* [G] */
+  uint64_t* rd_ctx;       /* [max_reads * G] k-major */
+  uint8_t* rd_from;       /* [max_reads * G] k-major */
+  uint8_t* xf_from;       /* [G] */
+  uint64_t* xf_term;      /* [G] */
+  /* dense: qb_propose_in */
+  uint8_t* action;        /* [G] */
+  uint32_t* n_ents;       /* [G] */
+  uint64_t* g_payload;    /* [G] */
+  uint32_t* g_cc_at;      /* [G] */
+  uint64_t* g_cc_payload; /* [G] */
+  uint8_t* gflags;        /* [G] QB_RWFLAG_* */
+  uint64_t* stats;        /* nullable: [QB_RWSTAT_COUNT] */
+} qb_request_wire_out;
+
+size_t qb_wire_requests_scratch_bytes(uint64_t G, uint64_t M); /* 0: too large for one call */
+int qb_dev_ingest_requests(uint64_t M, const uint8_t* bytes, uint64_t nbytes,
+                           const uint64_t* msg_off, const uint32_t* msg_group, uint64_t G,
+                           const uint32_t* off, const uint64_t* ids, uint32_t max_reads,
+                           uint32_t concat, const qb_request_wire_out* out, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* ----------------------------------------------------------------------- */
 /* Wire encode: Message.Marshal of the outboxes                            */
 /* ----------------------------------------------------------------------- */

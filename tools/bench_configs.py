@@ -2840,6 +2840,173 @@ def follower_wire_config(M, reps, *, reporter=None):
     assert ok, "follower wire parity failed"
 
 
+def request_wire_config(G, reps, *, reporter=None):
+    """The requests' wire ingest (qb_dev_ingest_requests) over G groups of
+    five voters, max_reads 4, concat on, three samples: (a) one batch of 2^20
+    messages — 70 % single-entry MsgProp with a 64-byte payload, 25 %
+    MsgReadIndex, 5 % MsgTransferLeader and MsgReadIndexResp — to random
+    groups; (b) the same mixture for G / 100 messages; (c) an idle call, M = 0.
+    Beside (a) and (b), in the same session, qb_dev_ingest_follower over the
+    same bytes (its kernels are the parent's, unchanged: every message decodes
+    and comes out QB_WIRE_TYPE), the nearest existing kernel of the same
+    shape.  One HIP event pair per call, median over the samples after warm-up;
+    calls straight to the C ABI.  Parity: tests/request_wire_ref.py's pass 1
+    over every 1024th message, and the counters' sums."""
+    reporter = reporter or report
+    import ctypes as C
+    import time
+    from etcd_amd import _lib
+    from etcd_amd.quorum import wire
+    from tests import request_wire_ref as RW
+    sp = torch.cuda.current_stream(dev).cuda_stream
+    n, R = 5, 4
+    ar = lambda k: torch.arange(k, dtype=torch.int64, device=dev)  # noqa: E731
+    gg, ss = ar(G).repeat_interleave(n), ar(n).repeat(G)
+    ids = 16384 + ss * 200000 + gg % 100000
+    off = (ar(G + 1) * n).to(torch.int32)
+    snap = [0x4A, len(wire._EMPTY_SNAPSHOT)] + list(wire._EMPTY_SNAPSHOT) + [0x50, 0, 0x58, 0]
+
+    def batch(M, seed):
+        """Host bytes of M messages in four fixed layouts, scattered in order."""
+        rng = np.random.default_rng(seed)
+        grp = rng.integers(0, G, M).astype(np.uint32)
+        g64 = grp.astype(np.uint64)
+        frm = np.uint64(16384) + rng.integers(1, n, M).astype(np.uint64) * np.uint64(200000) + \
+            g64 % np.uint64(100000)
+        to = np.uint64(16384) + g64 % np.uint64(100000)
+        ctx = (np.uint64(1) << np.uint64(56)) + rng.integers(1, 1 << 40, M).astype(np.uint64)
+        ctxb = ((ctx[:, None] >> (np.arange(7, -1, -1, dtype=np.uint64) * np.uint64(8)))
+                & np.uint64(0xFF)).astype(np.uint8)
+        u = rng.random(M)
+        cls = np.where(u < 0.70, 0, np.where(u < 0.95, 1, np.where(u < 0.975, 2, 3)))
+        col = lambda b: np.full((M, 1), b, np.uint8)  # noqa: E731
+        cols = lambda bs: [col(b) for b in bs]  # noqa: E731
+        head = lambda t, term, index: [col(0x08), col(t), col(0x10), wire._vfix(to, 3), col(0x18),  # noqa: E731
+                                       wire._vfix(frm, 3), col(0x20), *term, col(0x28), col(0),
+                                       col(0x30), *index]
+        ent8 = cols([0x3A, 16, 0x08, 0, 0x10, 0, 0x18, 0, 0x22, 8]) + [ctxb]
+        lay = [head(2, [col(0)], [col(0)]) + cols([0x3A, 72, 0x08, 0, 0x10, 0, 0x18, 0, 0x22, 64]) +
+               [np.tile(np.arange(64, dtype=np.uint8) + 0x30, (M, 1))] + cols([0x40, 0] + snap),
+               head(15, [col(0)], [col(0)]) + ent8 + cols([0x40, 0] + snap),
+               head(13, [wire._vfix(np.full(M, 20000, np.uint64), 3)], [col(0)]) + cols([0x40, 0] + snap),
+               head(16, [wire._vfix(np.full(M, 20000, np.uint64), 3)],
+                    [wire._vfix(np.uint64(1 << 35) + g64, 6)]) + ent8 + cols([0x40, 0] + snap)]
+        lay = [np.concatenate(x, axis=1) for x in lay]
+        lens = np.array([x.shape[1] for x in lay], np.uint64)[cls]
+        moff = np.zeros(M + 1, np.uint64)
+        np.cumsum(lens, out=moff[1:])
+        buf = np.empty(int(moff[-1]), np.uint8)
+        for k, t in enumerate(lay):
+            pos = moff[:-1][cls == k].astype(np.int64)
+            buf[(pos[:, None] + np.arange(t.shape[1])).reshape(-1)] = t[cls == k].reshape(-1)
+        return buf, moff, grp
+
+    def timed(call):
+        def sample(ev):
+            torch.cuda.synchronize()
+            ev.record(ev.ev[0], sp)
+            call()
+            ev.record(ev.ev[1], sp)
+            torch.cuda.synchronize()
+            return ev.elapsed_ms(0, 1) / 1e3
+        ev = HipEvents(2)
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < 0.3:  # warm-up: clocks settle (time_region)
+            sample(ev)
+        ts = [sample(ev) for _ in range(reps)]
+        ev.close()
+        return float(np.median(ts))
+
+    # Bytes a call must move (the columns the launches touch, not a traffic
+    # counter).  Per group: the zeroed count 4, the scan's two passes over it
+    # 16 (none with M = 0), pass 2's count read 4 and the nine dense defaults
+    # 36.  Per message: msg_off 8 and msg_group 4 read, its own bytes, the
+    # eighteen columns 82 and the count 4 (pass 1); status, kind, group 6 read
+    # and the index 4 written (scatter); the index 4 and the kind 1 read
+    # (pass 2), and what its kind takes from its columns and puts into the
+    # dense ones: a read 9 + 9 + 1, a proposal 24 + 4, a transfer 9.
+    PER_GROUP_IDLE, PER_GROUP, PER_MSG = 4 + 4 + 36, 4 + 16 + 4 + 36, 12 + 82 + 4 + 10 + 5
+    fn = _lib.fn("qb_dev_ingest_requests")
+    ffn = _lib.fn("qb_dev_ingest_follower")
+    stats = torch.zeros(len(wire.WIRE_REQUEST_STAT_NAMES), dtype=torch.int64, device=dev)
+    h = lambda t: t.cpu().numpy()  # noqa: E731
+    rows, ok, detail = {}, True, {}
+    for name, M in (("batch_1M", 1 << 20), ("one_percent", G // 100), ("idle", 0)):
+        buf, moff, grp = batch(max(M, 1), 0xBEEF + M)
+        if M == 0:
+            buf, moff, grp = buf[:1], moff[:1], grp[:0]
+        nb = int(moff[-1]) if M else 0
+        d_buf = torch.from_numpy(buf).to(dev)
+        d_moff = torch.from_numpy(moff.view(np.int64).copy()).to(dev)
+        d_grp = torch.from_numpy(np.resize(grp, max(M, 1)).view(np.int32).copy()).to(dev)
+        o = wire.new_request_out(M, G, R, dev)
+        rin, pin = o.request_in, o.propose_in
+        dense = {"n_reads": rin.n_reads, "rd_ctx": rin.rd_ctx, "rd_from": rin.rd_from,
+                 "xf_from": rin.xf_from, "xf_term": rin.xf_term, "action": pin.action,
+                 "n_ents": pin.n_ents, "g_payload": pin.payload, "g_cc_at": pin.cc_at,
+                 "g_cc_payload": pin.cc_payload, "gflags": o.gflags}
+        oc = wire.RequestWireOutC(*[getattr(o, "frm" if k == "from" else k).data_ptr() for k, _ in wire._RW_MSG],
+                                  *[dense[k].data_ptr() for k, _, _ in wire._RW_DENSE], stats.data_ptr())
+        need = int(_lib.fn("qb_wire_requests_scratch_bytes")(G, M))
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        call = lambda: _lib.check(fn(M, d_buf.data_ptr(), nb, d_moff.data_ptr(), d_grp.data_ptr(), G,  # noqa: E731,B023
+                                     off.data_ptr(), ids.data_ptr(), R, 1, C.byref(oc), ws.data_ptr(),  # noqa: B023
+                                     need, sp), "qb_dev_ingest_requests")  # noqa: B023
+        tm = timed(call)
+        stats.zero_()
+        call()
+        torch.cuda.synchronize()
+        st = h(stats).view(np.uint64)
+        taken = 19 * int(st[RW.STAT_TAKEN_READS]) + 28 * int(st[RW.STAT_TAKEN_PROPS]) + \
+            9 * int(st[RW.STAT_TAKEN_TRANSFERS])
+        by = G * (PER_GROUP if M else PER_GROUP_IDLE) + M * PER_MSG + nb + taken
+        rows[name] = {"messages": M, "us": tm * 1e6, "in_bytes": nb, "bytes": by, "TBs": by / tm / 1e12,
+                      "frac": by / tm / 1e9 / HBM_PEAK_GBS, "taken_props": int(st[RW.STAT_TAKEN_PROPS]),
+                      "taken_reads": int(st[RW.STAT_TAKEN_READS]), "deferred": int(st[RW.DEFERRED])}
+        ok = ok and int(st[:10].sum()) == M
+        # ---- parity: pass 1 of every 1024th message against the restatement ----
+        sub = list(range(0, M, 1024))
+        hid = h(ids).view(np.uint64)
+        got = {k: h(getattr(o, k)).view(dt) for k, dt in RW.COLUMNS} if M else {}
+        good = 0
+        for i in sub:
+            g = int(grp[i])
+            w = RW.decode(buf[int(moff[i]):int(moff[i + 1])].tobytes(), g, G, hid[n * g:n * g + n])
+            if w["ent_bytes"]:
+                w["ent_pos"] += int(moff[i])
+            same = all(int(got[k][i]) == w[k] for k, _ in RW.COLUMNS
+                       if k not in ("status", "rd_k", "ent_base"))
+            good += same and int(got["status"][i]) in (w["status"], RW.DEFERRED)
+        ok = ok and good == len(sub)
+        detail[name] = f"{good}/{len(sub)}"
+        if M:  # the follower's ingest over the same bytes, same session
+            fo = wire.new_follower_out(M, 0, dev)
+            ib, app = fo.inbox, fo.app
+            fc = wire.FollowerWireOutC(ib.group.data_ptr(), ib.flags.data_ptr(), ib.frm.data_ptr(),
+                                       ib.term.data_ptr(), ib.index.data_ptr(), ib.aux.data_ptr(),
+                                       app.commit.data_ptr(), fo.status.data_ptr(), fo.msg_type.data_ptr(),
+                                       fo.ent_pos.data_ptr(), fo.ent_bytes.data_ptr(), fo.ent_n.data_ptr(),
+                                       app.ent_off.data_ptr(), app.ent_term.data_ptr(),
+                                       app.ent_len.data_ptr(), 0, fo.ent_total.data_ptr(), None)
+            fneed = int(_lib.fn("qb_wire_follower_scratch_bytes")(M))
+            fws = torch.empty(max(fneed, 256), dtype=torch.uint8, device=dev)
+            tf = timed(lambda: _lib.check(ffn(M, d_buf.data_ptr(), nb, d_moff.data_ptr(), d_grp.data_ptr(),  # noqa: B023
+                                              G, C.byref(fc), fws.data_ptr(), fneed, sp),  # noqa: B023
+                                          "qb_dev_ingest_follower"))
+            fby = M * (12 + 67 + 16 + 9) + nb  # follower_wire_config's count, no runs
+            rows[name].update(follower_us=tf * 1e6, follower_bytes=fby, follower_TBs=fby / tf / 1e12)
+    extra = {"unit": "messages/s", "samples": reps, "groups": G, "max_reads": R, "concat": 1,
+             "timing": "one HIP event pair per call, median over the samples after warm-up",
+             **{f"{k}_{f}": v for k, r in rows.items() for f, v in r.items()},
+             "parity": bool(ok),
+             "parity_check": f"tests/request_wire_ref.py pass 1 over every 1024th message, and the "
+                             f"status counters' sum: {detail}"}
+    r = rows["batch_1M"]
+    reporter("request wire ingest (2^20 messages: 70 % MsgProp, 25 % MsgReadIndex)", r["messages"],
+             r["us"] / 1e6, r["bytes"], extra)
+    assert ok, "request wire parity failed"
+
+
 def log_compact_config(G, reps, *, reporter=None):
     """The batched CreateSnapshot / Compact (qb_dev_log_compact, explicit mode)
     over G groups.  The call reads no per-slot state, so the voter count of the
@@ -3044,6 +3211,8 @@ def main():
         snapshot_config(1 << 22, a.reps)
     if "log-compact" in which:
         log_compact_config(1 << 22, a.reps)
+    if "wire-requests" in which:
+        request_wire_config(1 << 22, a.reps)
     if "encode" in which:
         encode_config(1 << 22, a.reps)
     if "follower-wire" in which:
